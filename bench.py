@@ -5,7 +5,12 @@ zstd level-3 compression of a batch of 65 536 x 64 KiB slices (seeded synthetic
 HBM when the timed region starts.  One step = one pass of the whole hot path
 (match kernel + entropy/frame kernel) over the batch.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--config 1|3] [--slices M]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--config 1|3] [--slices M] [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the line: value, ms_per_step and the figures read off those
+steps.  --full adds everything else the bench measures or checks (the CPU baselines, the PCIe figure, the decode /
+DEFLATE / inflate legs, the streaming entry point, N > 1's scatter + gather-v figure).  --dump-outputs DIR writes what
+the last timed step computed as DIR/*.npy (see dump_outputs), so that two builds can be compared output for output.
 
 N > 1: one rank per GPU over RCCL.  Started by torch.distributed.run (RANK / LOCAL_RANK / WORLD_SIZE in the
 environment) the process is a rank; started plainly with --gpus N > 1 it starts those N ranks itself as child
@@ -332,6 +337,50 @@ def cpu_codec_baseline(kind, base, offs, lens, n, cap, what, out_bytes_per_entry
     return res
 
 
+DUMP_BUDGET = 60 << 20         # bytes of .npy payload --dump-outputs may write (the limit is 64 MB)
+
+
+def dump_outputs(out_dir, prefix, buf, offs, lens, entry_cap):
+    """--dump-outputs: the entries the last timed step left in `buf` (entry i = buf[offs[i] : offs[i] + lens[i]], as its caller
+    receives them) as float arrays under out_dir:
+      <prefix>_sizes.npy         float64 [n]  every entry's length in bytes
+      <prefix>_checksums.npy     float64 [n]  every entry's sum of byte * (position in the entry % 251 + 1), exact in float64
+      <prefix>_sample_index.npy  float64 [k]  a fixed, seeded sample of the entries (the same for the same arguments)
+      <prefix>_sample_bytes.npy  float32 [.]  those entries' bytes, back to back in sample order
+    k is set by the batch shape alone (n, entry_cap), so that the whole dump stays under DUMP_BUDGET."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    n = int(lens.numel())
+    offs_h = offs[:n].cpu().numpy().astype(np.int64)
+    lens_h = lens[:n].cpu().numpy().astype(np.int64)
+    if n and (lens_h.min() < 0 or int((offs_h + lens_h).max()) > buf.numel()):
+        raise SystemExit(f"bench.py --dump-outputs: {prefix} entries run outside their buffer")
+    sums = np.zeros(n, dtype=np.float64)
+    width = int(lens_h.max()) if n else 0
+    if width:
+        pos = torch.arange(width, dtype=torch.int64, device=buf.device)
+        weight = pos % 251 + 1
+        rows = max(1, (1 << 24) // width)
+        for lo in range(0, n, rows):
+            hi = min(n, lo + rows)
+            o = offs[lo:hi].to(torch.int64).unsqueeze(1)
+            ln = lens[lo:hi].to(torch.int64).unsqueeze(1)
+            inside = pos.unsqueeze(0) < ln
+            idx = torch.where(inside, o + pos.unsqueeze(0), torch.zeros_like(o))
+            v = buf[idx].to(torch.int64) * weight.unsqueeze(0)
+            sums[lo:hi] = torch.where(inside, v, torch.zeros_like(v)).sum(dim=1).cpu().numpy()
+    k = min(n, max(1, (DUMP_BUDGET - 16 * n) // (4 * max(1, entry_cap))))
+    pick = np.sort(np.random.default_rng(20240607).choice(n, size=k, replace=False)) if n else np.zeros(0, dtype=np.int64)
+    parts = [buf[int(offs_h[i]):int(offs_h[i] + lens_h[i])].cpu().numpy() for i in pick]
+    sample = np.concatenate(parts).astype(np.float32) if parts else np.zeros(0, dtype=np.float32)
+    np.save(os.path.join(out_dir, f"{prefix}_sizes.npy"), lens_h.astype(np.float64))
+    np.save(os.path.join(out_dir, f"{prefix}_checksums.npy"), sums)
+    np.save(os.path.join(out_dir, f"{prefix}_sample_index.npy"), pick.astype(np.float64))
+    np.save(os.path.join(out_dir, f"{prefix}_sample_bytes.npy"), sample)
+    print(f"bench.py --dump-outputs: {n} {prefix} entries, {k} sampled ({sample.size} bytes) -> {out_dir}", file=sys.stderr, flush=True)
+
+
 def extra_legs(b, torch, np, src, in_off, in_len, dst, out_off, out_len, host, n, dev, no_cpu, steps=3):
     """The other single-GPU BASELINE configs on the same batch, after the headline's timed region: configs[2] (ZstdDecompressor
     over the frames just written), configs[4] (raw DEFLATE level 6) and inflate of its streams.  Each: `steps` timed passes after
@@ -498,7 +547,17 @@ def main():
     ap.add_argument("--deflate-level", type=int, default=None, help="zlib level of --mode deflate / inflate (1 .. 9, default 6 = BASELINE configs[4])")
     ap.add_argument("--mode", choices=["compress", "decompress", "deflate", "inflate"], default="compress",
                     help="compress = BASELINE configs[1] (the headline); decompress = configs[2] over the same frames; deflate = configs[4] (raw DEFLATE level 6); inflate = ZlibDecompressor over configs[4]'s streams")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not need: CPU baselines, the PCIe figure, the decode / DEFLATE / inflate legs, "
+                         "the streaming entry point, N > 1's scatter + gather-v figure (each can still be left out with its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (float32 / float64, at most 64 MB)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if not args.full:
+        # a plain run: the headline's set-up, warm-up and timed steps, nothing else
+        args.no_cpu = args.no_pcie = args.no_extra = args.no_stream = args.no_exchange = True
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args.gpus))
     if args.slices <= 0:
@@ -604,6 +663,7 @@ def main():
             raise SystemExit("--deflate-level 1 .. 9")
         dwb, dml = args.deflate_window_bits, args.deflate_mem_level
         dparams = dict(window_bits=dwb, mem_level=dml)
+        dstride = b.out_stride
         if (dwb, dml) != (15, 8):
             # other settings than zlib's defaults may expand a slice by an eighth (kmp_deflate_bound_params): wider strides
             dstride = (int(b.lib.kmp_deflate_bound_params(SLICE, dwb, dml)) + 63) & ~63
@@ -625,6 +685,8 @@ def main():
                 _, _, l2, st_ = b.inflate(dst, out_off, out_len, cap, dst=back, out_off=in_off)
             e1.record(); torch.cuda.synchronize()
             dt = time.perf_counter() - t0
+            if args.dump_outputs:
+                dump_outputs(args.dump_outputs, "inflated", back, in_off, l2, SLICE)
             ok = bool(int(st_.abs().sum().item()) == 0 and torch.equal(back[: n * SLICE], src))
             ms_pipe = e0.elapsed_time(e1) / args.steps
             algo = n * SLICE + int(lens.sum())
@@ -653,6 +715,8 @@ def main():
             b.deflate(src, in_off, in_len, dst, out_off, out_len, level=dlevel, **dparams)
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, "streams", dst, out_off, out_len, dstride)
         kms = b.deflate_kernel_ms()
         lens = out_len.cpu().numpy().astype(np.int64)
         # spot check against the host's zlib
@@ -802,6 +866,9 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
 
+    if args.dump_outputs and args.mode == "compress" and rank == 0:
+        # the frames as the step hands them over: densely packed, frame i at dense_off[i]
+        dump_outputs(args.dump_outputs, "frames", dense, dense_off, out_len, b.out_stride)
     lens = out_len.cpu().numpy().astype(np.int64)
     frame_bytes = int(lens.sum())
     in_bytes = n * SLICE
@@ -926,6 +993,8 @@ def main():
             kd.append(b.last_kernel_ms(2))
         fence()
         dt = time.perf_counter() - t0
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, "decoded", back, in_off, l2, SLICE)
         ok = bool(int(st.abs().sum().item()) == 0 and torch.equal(back[: n * SLICE], src))
         if rank == 0:
             ms_dec = float(np.mean(kd))

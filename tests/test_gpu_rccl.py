@@ -85,7 +85,7 @@ def test_bench_gpus_1_through_the_distributed_path():
     env["KMP_BENCH_FORCE_DIST"] = "1"
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1", "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
-           os.path.join(ROOT, "bench.py"), "--gpus", "1", "--slices", "4096", "--steps", "2", "--warmup", "1", "--no-cpu", "--no-stream", "--no-pcie", "--no-extra"]
+           os.path.join(ROOT, "bench.py"), "--gpus", "1", "--slices", "4096", "--steps", "2", "--warmup", "1", "--full", "--no-cpu", "--no-stream", "--no-pcie", "--no-extra"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=540, env=env, cwd=ROOT)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-2000:])
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

@@ -3,7 +3,7 @@
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$R/gpurun_out/bench_lines.txt
 : > $O
-run() { echo "## python bench.py $*" >> $O; timeout -k 10 400 python $R/bench.py "$@" 2>/dev/null | tail -n 1 >> $O; echo >> $O; }
+run() { echo "## python bench.py $*" >> $O; timeout -k 10 400 python $R/bench.py --full "$@" 2>/dev/null | tail -n 1 >> $O; echo >> $O; }
 run --steps 5 --warmup 2
 run --config 3 --steps 3 --warmup 1 --no-cpu --no-stream
 run --mode decompress --steps 5 --warmup 2 --no-cpu

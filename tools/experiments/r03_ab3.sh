@@ -12,5 +12,5 @@ run KMP_MATCH_V2=2 KMP_TABLE_SPAN_GIB=80
 run KMP_MATCH_V2=0 KMP_TABLE_ARENA=0
 run KMP_MATCH_V2=0
 echo "## default line" >> $O
-timeout -k 10 400 python $R/bench.py >> $O 2>&1
+timeout -k 10 400 python $R/bench.py --full >> $O 2>&1
 echo done >> $O
