@@ -18,6 +18,7 @@
 
 #include <mutex>
 #include <new>
+#include <type_traits>
 #include <vector>
 
 // --------------------------------------------------------------------------
@@ -150,6 +151,18 @@ __global__ __launch_bounds__(256) void k_len_guard_finish(const u32* in_len, u32
     else if (meta && meta[i].status == 3u) { out_len[i] = 0; atomicOr(status, (u32)KMP_STATUS_LEVEL_SIZE); }
     else if (meta && in_len[i] >= 8 && meta[i].status != 0) { out_len[i] = 0; atomicOr(status, (u32)KMP_STATUS_KERNEL_GUARD); }
 }
+// The parsers are templates on their team width (lanes per slice): f(std::integral_constant<int, G>()) for G = 2 .. 64 (else 64)
+template <class F> static void by_team_width(int G, F const& f)
+{
+    switch (G) {
+    case 2:  f(std::integral_constant<int, 2>()); break;
+    case 4:  f(std::integral_constant<int, 4>()); break;
+    case 8:  f(std::integral_constant<int, 8>()); break;
+    case 16: f(std::integral_constant<int, 16>()); break;
+    case 32: f(std::integral_constant<int, 32>()); break;
+    default: f(std::integral_constant<int, 64>()); break;
+    }
+}
 
 // --------------------------------------------------------------------------
 // errors
@@ -183,14 +196,13 @@ extern "C" int kmp_debug_probe_region(void* p, size_t bytes, uint32_t blocks, ui
 {
     if (!p || bytes < 4096 || !ms) { g_last_error = "kmp_debug_probe_region: bad argument"; return KMP_ERR_ARG; }
     hipStream_t const st = (hipStream_t)hip_stream;
-    hipEvent_t e0, e1; HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1));
+    hip_event e0, e1; KMP_TRY(e0.create(hipEventDefault)); KMP_TRY(e1.create(hipEventDefault));
     hipLaunchKernelGGL(k_region_probe, dim3(blocks), dim3(256), 0, st, (u32*)p, (u64)(bytes / 4), 8u, 1u);       // warm
     HIP_TRY(hipEventRecord(e0, st));
     hipLaunchKernelGGL(k_region_probe, dim3(blocks), dim3(256), 0, st, (u32*)p, (u64)(bytes / 4), iters, 7u);
     HIP_TRY(hipEventRecord(e1, st));
     HIP_TRY(hipEventSynchronize(e1));
     HIP_TRY(hipEventElapsedTime(ms, e0, e1));
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
     return KMP_OK;
 }
 // What the memory system gives the level-3 parser's tables WHERE THEY LIE: random accesses over the context's table pieces,
@@ -233,14 +245,14 @@ u32 env_u32(const char* name, u32 dflt)
 // (k_region_probe, ~30 ms each) until one is of the fast kind, the fastest stays, the others are freed.  The default is one
 // plain allocation: the candidates of a trial are held until the choice is made, and a library must not take that much
 // memory behind its caller's back.
-static int place_alloc(u32** out, size_t bytes, float* kept_ms, u32* tried_out)
+static int place_alloc(dev_buf<u32>& out, size_t bytes, float* kept_ms, u32* tried_out)
 {
     u32 tries = KMP_KNOB("KMP_PLACE_TRIES", 1); if (tries < 1) tries = 1; if (tries > 8) tries = 8;
     if (bytes < ((size_t)4 << 30)) tries = 1;
-    u32* cand[8] = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr }; float ms[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
+    dev_buf<u32> cand[8]; float ms[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
     u32 got = 0, best = 0;
     for (u32 t = 0; t < tries; t++) {
-        if (hipMalloc((void**)&cand[t], bytes) != hipSuccess) { (void)hipGetLastError(); cand[t] = nullptr; break; }
+        if (cand[t].alloc(bytes) != KMP_OK) break;
         got = t + 1;
         if (tries > 1 && kmp_debug_probe_region(cand[t], bytes, 4096u, 384u, &ms[t], nullptr) != KMP_OK) ms[t] = 1e30f;
         if (ms[t] < ms[best]) best = t;
@@ -249,8 +261,8 @@ static int place_alloc(u32** out, size_t bytes, float* kept_ms, u32* tried_out)
     }
     if (got == 0) return hip_fail(hipErrorOutOfMemory, "hipMalloc(parser tables)");
     if (env_u32("KMP_VERBOSE", 0)) { fprintf(stderr, "place_alloc %zu MiB:", bytes >> 20); for (u32 t = 0; t < got; t++) fprintf(stderr, " %.1f ms%s", ms[t], t == best ? "*" : ""); fprintf(stderr, "\n"); }
-    for (u32 t = 0; t < got; t++) if (t != best) (void)hipFree(cand[t]);
-    *out = cand[best];
+    for (u32 t = 0; t < got; t++) if (t != best) cand[t].reset();
+    out = std::move(cand[best]);
     if (kept_ms) *kept_ms = ms[best];
     if (tried_out) *tried_out = got;
     return KMP_OK;
@@ -258,7 +270,6 @@ static int place_alloc(u32** out, size_t bytes, float* kept_ms, u32* tried_out)
 
 struct create_opts { int span_gib; int retry; };          // -1 = the environment's / the default
 static int batch_create_body(kmp_batch_ctx* c, int device, uint32_t max_slices, uint32_t max_slice_bytes, int team_lanes, create_opts const& o);
-extern "C" void kmp_batch_destroy(kmp_batch_ctx* c);
 static int batch_create_with(kmp_batch_ctx** out, int device, uint32_t max_slices, uint32_t max_slice_bytes, int team_lanes, create_opts const& o)
 {
     if (!out || max_slices == 0) { g_last_error = "kmp_batch_create: bad argument"; return KMP_ERR_ARG; }
@@ -267,13 +278,11 @@ static int batch_create_with(kmp_batch_ctx** out, int device, uint32_t max_slice
     if (team_lanes == 0) team_lanes = (int)env_u32("KMP_TEAM_LANES", 4);
     if (team_lanes != 2 && team_lanes != 4 && team_lanes != 8 && team_lanes != 16 && team_lanes != 32 && team_lanes != 64) { g_last_error = "team_lanes must be 2, 4, 8, 16, 32 or 64"; return KMP_ERR_ARG; }
     HIP_TRY(hipSetDevice(device));
-    kmp_batch_ctx* c = new (std::nothrow) kmp_batch_ctx();
+    std::unique_ptr<kmp_batch_ctx> c(new (std::nothrow) kmp_batch_ctx());
     if (!c) { g_last_error = "out of host memory"; return KMP_ERR_ARG; }
-    memset(c, 0, sizeof(*c));
     c->team_fixed = team_fixed;
-    int const rc = batch_create_body(c, device, max_slices, max_slice_bytes, team_lanes, o);
-    if (rc != KMP_OK) { std::string const keep = g_last_error; kmp_batch_destroy(c); g_last_error = keep; return rc; }      // nothing half-built is left behind
-    *out = c;
+    KMP_TRY(batch_create_body(c.get(), device, max_slices, max_slice_bytes, team_lanes, o));      // (nothing half-built is left behind)
+    *out = c.release();
     return KMP_OK;
 }
 extern "C" int kmp_batch_create(kmp_batch_ctx** out, int device, uint32_t max_slices, uint32_t max_slice_bytes, int team_lanes)
@@ -299,7 +308,7 @@ static int batch_create_body(kmp_batch_ctx* c, int device, uint32_t max_slices, 
     hipDeviceProp_t prop; HIP_TRY(hipGetDeviceProperties(&prop, device));
     // the context's own stream: the second stream of its pipelines, and where creation's probes and clears run (non-blocking:
     // nothing here serialises with the caller's streams, the NULL stream included)
-    HIP_TRY(hipStreamCreateWithFlags(&c->st2, hipStreamNonBlocking));
+    KMP_TRY(c->st2.create(hipStreamNonBlocking));
     u32 const waves_per_cu = KMP_KNOB("KMP_MATCH_WAVES_PER_CU", 16);     // 16 x 16 teams x 256 CUs = 65 536 slices in flight at team width 4
     u32 const teams_per_wave = 64 / (u32)team_lanes;
     u32 blocks = (u32)prop.multiProcessorCount * waves_per_cu;
@@ -318,11 +327,11 @@ static int batch_create_body(kmp_batch_ctx* c, int device, uint32_t max_slices, 
     if (c->big) {
         c->big_G = (int)KMP_KNOB("KMP_BIG_TEAM_LANES", 0);      // 0 = by batch size (zstd_compress_big)
         if (c->big_G != 0 && c->big_G != 2 && c->big_G != 4 && c->big_G != 8 && c->big_G != 16 && c->big_G != 32 && c->big_G != 64) c->big_G = 0;
-        HIP_TRY(hipMalloc((void**)&c->fstate, ns * sizeof(KFrameState)));
-        HIP_TRY(hipMalloc((void**)&c->hufct, ns * 512 * sizeof(u32)));
-        { int const rc = place_alloc(&c->big_tables, ns * KX_BIG_TBL_ENTRIES * sizeof(u32), nullptr, nullptr); if (rc != KMP_OK) return rc; }     // (the block-chain parser's tables: the same access pattern)
-        HIP_TRY(hipMalloc((void**)&c->remaining, 64));
-        HIP_TRY(hipMalloc((void**)&c->big_counters, ns * 4));
+        KMP_TRY(c->fstate.alloc(ns * sizeof(KFrameState), "hipMalloc(frame states)"));
+        KMP_TRY(c->hufct.alloc(ns * 512 * sizeof(u32), "hipMalloc(Huffman tables)"));
+        KMP_TRY(place_alloc(c->big_tables, ns * KX_BIG_TBL_ENTRIES * sizeof(u32), nullptr, nullptr));     // (the block-chain parser's tables: the same access pattern)
+        KMP_TRY(c->remaining.alloc(64, "hipMalloc(open frames)"));
+        KMP_TRY(c->big_counters.alloc(ns * 4, "hipMalloc(block-chain counters)"));
     }
     {
         // The workspace of a context with large team tables is ONE allocation (an arena): the tables in four pieces (team t:
@@ -354,8 +363,7 @@ static int batch_create_body(kmp_batch_ctx* c, int device, uint32_t max_slices, 
             if (want > need && fr < want + ((size_t)16 << 30)) want = 0;    // not that much room: pack
             size_t const gap = want > need ? ((want - need) / 3) & ~(A - 1) : 0;     // unused bytes behind each of the three buffers between the pieces (rounded down: the span is a bound)
             size_t const total = need + 3 * gap;
-            if (fr > total + ((size_t)1 << 30) && hipMalloc((void**)&c->arena, total) == hipSuccess) {
-                c->arena_bytes = total;
+            if (fr > total + ((size_t)1 << 30) && c->arena.alloc(total) == KMP_OK) {
                 // Where in the arena the four pieces go is chosen by measurement, inside the arena (nothing else is allocated):
                 // up to eight layouts are probed with the tables' own traffic (k_table_probe, read + insert pairs, ~12 ms each) and
                 // the fastest stays.  Which physical blocks of the HBM an offset of the arena falls into differs from process to
@@ -396,8 +404,8 @@ static int batch_create_body(kmp_batch_ctx* c, int device, uint32_t max_slices, 
                 u32 const fixed = KMP_KNOB("KMP_TABLE_LAYOUT", 0);
                 // probes every layout on the arena at `base`: the fastest one (priced with the parser's own mix) and its pair rate
                 auto probe_arena = [&](u8* base, u32* best_l, float* best_ms, float* best_pairs) -> int {
-                    hipEvent_t e[3] = { nullptr, nullptr, nullptr };
-                    for (int i = 0; i < 3; i++) if (hipEventCreate(&e[i]) != hipSuccess) { for (int j = 0; j < i; j++) (void)hipEventDestroy(e[j]); g_last_error = "kmp_batch_create: hipEventCreate failed"; return KMP_ERR_HIP; }
+                    hip_event e[3];
+                    for (int i = 0; i < 3; i++) KMP_TRY(e[i].create(hipEventDefault));
                     u64 const words = (u64)(piece / 4); u32 const pb = (u32)prop.multiProcessorCount * 16u;
                     int rc = KMP_OK; *best_ms = 1e30f; *best_l = 0; *best_pairs = 0;
                     for (u32 l = 0; l < nlay && rc == KMP_OK; l++) {
@@ -417,7 +425,6 @@ static int batch_create_body(kmp_batch_ctx* c, int device, uint32_t max_slices, 
                         if (env_u32("KMP_VERBOSE", 0)) fprintf(stderr, "arena %p layout %u: %.1f G pairs/s, %.1f G reads/s\n", (void*)base, l + 1, pairs / 1e9, (double)pb * 64.0 * 96.0 * 4.0 / (msr * 1e-3) / 1e9);
                         if (ms < *best_ms) { *best_ms = ms; *best_l = l; *best_pairs = pairs; }
                     }
-                    for (int i = 0; i < 3; i++) (void)hipEventDestroy(e[i]);
                     return rc;
                 };
                 if (fixed >= 1 && fixed <= nlay) pick = fixed - 1;
@@ -432,15 +439,14 @@ static int batch_create_body(kmp_batch_ctx* c, int device, uint32_t max_slices, 
                     size_t fr2 = 0, tot2 = 0;
                     u32 const retry = o.retry >= 0 ? (u32)o.retry : env_u32("KMP_TABLE_RETRY", 0);     // 0 never (the default), 1 when slow, 2 always (tests)
                     if ((pr1 < (float)KMP_KNOB("KMP_TABLE_RETRY_BELOW", 235) * 1e8f || retry == 2) && retry && hipMemGetInfo(&fr2, &tot2) == hipSuccess && fr2 > total + ((size_t)16 << 30)) {
-                        u8* second = nullptr;
-                        if (hipMalloc((void**)&second, total) == hipSuccess) {
+                        dev_buf<u8> second;
+                        if (second.alloc(total) == KMP_OK) {
                             u32 pick2 = 0; float ms2 = 0, pr2 = 0;
-                            int const rc = probe_arena(second, &pick2, &ms2, &pr2);
-                            if (rc != KMP_OK) { (void)hipFree(second); return rc; }
+                            KMP_TRY(probe_arena(second, &pick2, &ms2, &pr2));
                             if (env_u32("KMP_VERBOSE", 0)) fprintf(stderr, "arena retry: %.1f -> %.1f G pairs/s\n", pr1 / 1e9, pr2 / 1e9);
-                            if (ms2 < ms1 * 0.98f) { (void)hipFree(c->arena); c->arena = second; pick = pick2; c->table_retry = 2; }
-                            else { (void)hipFree(second); c->table_retry = 1; }
-                        } else (void)hipGetLastError();
+                            if (ms2 < ms1 * 0.98f) { c->arena.reset(); c->arena = std::move(second); pick = pick2; c->table_retry = 2; }
+                            else { second.reset(); c->table_retry = 1; }
+                        }
                     }
                 }
                 c->table_layout = pick + 1;
@@ -448,22 +454,22 @@ static int batch_create_body(kmp_batch_ctx* c, int device, uint32_t max_slices, 
                 // the other buffers: first fit into what the pieces leave free
                 if (nlay == 0 || !fits(lay[pick], &c->seqs, &c->lits, &c->meta, &c->scratch)) { g_last_error = "kmp_batch_create: arena layout failed"; return KMP_ERR_ARG; }
                 c->tseg_n = 4; c->tables = c->tseg[0];
-            } else { (void)hipGetLastError(); c->arena = nullptr; }
+            } else (void)hipGetLastError();
         }
         if (!c->arena) {
-            HIP_TRY(hipMalloc((void**)&c->seqs, ns * c->seq_cap * sizeof(KSeq)));
-            HIP_TRY(hipMalloc((void**)&c->lits, ns * c->lit_cap));
-            HIP_TRY(hipMalloc((void**)&c->meta, ns * sizeof(KSliceMeta)));
-            HIP_TRY(hipMalloc((void**)&c->scratch, ns * c->scratch_words * sizeof(u32)));
-            int const rc = place_alloc(&c->tables, tbytes, &c->place_ms, &c->place_tried); if (rc != KMP_OK) return rc;
-            c->tseg[0] = c->tables;
+            KMP_TRY(c->seqs_buf.alloc(ns * c->seq_cap * sizeof(KSeq), "hipMalloc(sequences)")); c->seqs = c->seqs_buf;
+            KMP_TRY(c->lits_buf.alloc(ns * c->lit_cap, "hipMalloc(literals)")); c->lits = c->lits_buf;
+            KMP_TRY(c->meta_buf.alloc(ns * sizeof(KSliceMeta), "hipMalloc(slice records)")); c->meta = c->meta_buf;
+            KMP_TRY(c->scratch_buf.alloc(ns * c->scratch_words * sizeof(u32), "hipMalloc(scratch)")); c->scratch = c->scratch_buf;
+            KMP_TRY(place_alloc(c->tables_buf, tbytes, &c->place_ms, &c->place_tried));
+            c->tables = c->tseg[0] = c->tables_buf;
         }
     }
-    HIP_TRY(hipMalloc((void**)&c->team_epoch, (size_t)c->nteams * sizeof(u32)));
-    HIP_TRY(hipMalloc((void**)&c->counter, 64));
+    KMP_TRY(c->team_epoch.alloc((size_t)c->nteams * sizeof(u32), "hipMalloc(team epochs)"));
+    KMP_TRY(c->counter.alloc(64, "hipMalloc(work counters)"));
     if ((size_t)c->nteams * KX_TBL_ENTRIES * sizeof(u32) >= ((size_t)4 << 30) && KMP_KNOB("KMP_TABLE_PROBE", 1)) {
         // ~40 ms: the two rates the parser lives on, measured on these very tables (they are zeroed right below)
-        hipEvent_t e[3]; for (int i = 0; i < 3; i++) HIP_TRY(hipEventCreate(&e[i]));
+        hip_event e[3]; for (int i = 0; i < 3; i++) KMP_TRY(e[i].create(hipEventDefault));
         u64 const words = (u64)c->nteams * KX_TBL_ENTRIES / c->tseg_n; u32 const blocks = (u32)prop.multiProcessorCount * 16u, iters = 96u;
         u32* const t1 = c->tseg_n == 4 ? c->tseg[1] : c->tseg[0]; u32* const t2 = c->tseg_n == 4 ? c->tseg[2] : c->tseg[0]; u32* const t3 = c->tseg_n == 4 ? c->tseg[3] : c->tseg[0];
         hipLaunchKernelGGL(k_table_probe, dim3(blocks), dim3(64), 0, c->st2, c->tseg[0], t1, t2, t3, c->tseg_n, words, 8u, 1u, c->counter);     // warm (TLB)
@@ -477,22 +483,20 @@ static int batch_create_body(kmp_batch_ctx* c, int device, uint32_t max_slices, 
         double const ops = (double)blocks * 64.0 * iters * 4.0;
         if (ms0 > 0) c->table_reads_per_s = (float)(ops / (ms0 * 1e-3));
         if (ms1 > 0) c->table_pairs_per_s = (float)(ops / (ms1 * 1e-3));
-        for (int i = 0; i < 3; i++) (void)hipEventDestroy(e[i]);
     }
     for (u32 i = 0; i < c->tseg_n; i++) HIP_TRY(hipMemsetAsync(c->tseg[i], 0, (size_t)c->nteams * KX_TBL_ENTRIES * sizeof(u32) / c->tseg_n, c->st2));
     HIP_TRY(hipMemsetAsync(c->team_epoch, 0, (size_t)c->nteams * sizeof(u32), c->st2));
     HIP_TRY(hipMemsetAsync(c->meta, 0, ns * sizeof(KSliceMeta), c->st2));
-    for (int i = 0; i < 14; i++) HIP_TRY(hipEventCreate(&c->ev[i]));
-    for (int i = 0; i < KMP_MAX_CHUNKS; i++) for (int j = 0; j < 2; j++) { HIP_TRY(hipEventCreate(&c->evm[i][j])); HIP_TRY(hipEventCreate(&c->eve[i][j])); }
-    HIP_TRY(hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming));
-    HIP_TRY(hipEventCreate(&c->tune_ev[0])); HIP_TRY(hipEventCreate(&c->tune_ev[1]));
-    HIP_TRY(hipEventCreateWithFlags(&c->ev_last_match, hipEventDisableTiming));
-    HIP_TRY(hipEventCreateWithFlags(&c->ev_done, hipEventDisableTiming));
-    for (int i = 0; i < KMP_MAX_PIECES; i++) HIP_TRY(hipEventCreateWithFlags(&c->ev_piece[i], hipEventDisableTiming));
-    for (int i = 0; i <= KMP_MAX_CHUNKS; i++) HIP_TRY(hipEventCreateWithFlags(&c->ev_pre[i], hipEventDisableTiming));
+    for (kmp_span* t : { &c->decode_t, &c->deflate_t, &c->tune }) { KMP_TRY(t->start.create(hipEventDefault)); KMP_TRY(t->end.create(hipEventDefault)); }
+    for (hip_event* e : { &c->dfl_mark.chains, &c->dfl_mark.best, &c->dfl_mark.best_done, &c->dfl_mark.parse, &c->dfl_mark.encode, &c->dfl_mark.encode_done }) KMP_TRY(e->create(hipEventDefault));
+    for (int i = 0; i < KMP_MAX_CHUNKS; i++) for (kmp_span* t : { &c->match[i], &c->entropy[i] }) { KMP_TRY(t->start.create(hipEventDefault)); KMP_TRY(t->end.create(hipEventDefault)); }
+    KMP_TRY(c->ev_join.create(hipEventDisableTiming));
+    KMP_TRY(c->ev_done.create(hipEventDisableTiming));
+    for (int i = 0; i < KMP_MAX_PIECES; i++) KMP_TRY(c->ev_piece[i].create(hipEventDisableTiming));
+    for (int i = 0; i <= KMP_MAX_CHUNKS; i++) KMP_TRY(c->ev_pre[i].create(hipEventDisableTiming));
     c->cus = (u32)prop.multiProcessorCount;
-    HIP_TRY(hipMalloc((void**)&c->len_ok, ns * sizeof(u32)));
-    HIP_TRY(hipMalloc((void**)&c->d_status, 64));
+    KMP_TRY(c->len_ok.alloc(ns * sizeof(u32), "hipMalloc(slice lengths)"));
+    KMP_TRY(c->d_status.alloc(64, "hipMalloc(status word)"));
     HIP_TRY(hipMemsetAsync(c->d_status, 0, 64, c->st2));
     c->knob.chunks = KMP_KNOB("KMP_ZSTD_CHUNKS", 0); c->knob.match_flags = KMP_KNOB("KMP_MATCH_FLAGS", 6); c->knob.entropy_pad = KMP_KNOB("KMP_ENTROPY_PAD_LDS", 0);
     c->knob.first_permille = KMP_KNOB("KMP_ZSTD_FIRST_PERMILLE", 500); c->knob.fast_first_permille = KMP_KNOB("KMP_ZSTD_FAST_FIRST_PERMILLE", 550); c->knob.entropy_flags = KMP_KNOB("KMP_ENTROPY_FLAGS", 0);
@@ -514,29 +518,6 @@ extern "C" void kmp_batch_destroy(kmp_batch_ctx* c)
 {
     if (!c) return;
     (void)hipSetDevice(c->device);
-    if (c->arena) (void)hipFree(c->arena);                                        // (holds seqs, lits, meta, scratch and the table pieces)
-    else { (void)hipFree(c->seqs); (void)hipFree(c->lits); (void)hipFree(c->meta); (void)hipFree(c->scratch); (void)hipFree(c->tables); }
-    (void)hipFree(c->tables_flat); (void)hipFree(c->team_epoch_flat);
-    (void)hipFree(c->team_epoch); (void)hipFree(c->tables4); (void)hipFree(c->epoch4); (void)hipFree(c->big_tables4);
-    (void)hipFree(c->d_dict); (void)hipFree(c->d_dictL); (void)hipFree(c->d_dictS); (void)hipFree(c->d_prior); (void)hipFree(c->d_dprior);
-    (void)hipFree(c->lz_srt); (void)hipFree(c->lz_wr); (void)hipFree(c->lz_order);
-    (void)hipFree(c->fstate); (void)hipFree(c->hufct); (void)hipFree(c->big_tables); (void)hipFree(c->remaining); (void)hipFree(c->big_counters); (void)hipFree(c->counter);
-    for (int i = 0; i < 14; i++) if (c->ev[i]) (void)hipEventDestroy(c->ev[i]);
-    for (int i = 0; i < KMP_MAX_CHUNKS; i++) for (int j = 0; j < 2; j++) { if (c->evm[i][j]) (void)hipEventDestroy(c->evm[i][j]); if (c->eve[i][j]) (void)hipEventDestroy(c->eve[i][j]); }
-    if (c->ev_join) (void)hipEventDestroy(c->ev_join);
-    for (int i = 0; i < 2; i++) if (c->tune_ev[i]) (void)hipEventDestroy(c->tune_ev[i]);
-    if (c->ev_last_match) (void)hipEventDestroy(c->ev_last_match);
-    if (c->ev_done) (void)hipEventDestroy(c->ev_done);
-    for (int i = 0; i < KMP_MAX_PIECES; i++) if (c->ev_piece[i]) (void)hipEventDestroy(c->ev_piece[i]);
-    for (int i = 0; i <= KMP_MAX_CHUNKS; i++) if (c->ev_pre[i]) (void)hipEventDestroy(c->ev_pre[i]);
-    (void)hipFree(c->len_ok); (void)hipFree(c->d_status);
-    (void)hipFree(c->pre_stage); (void)hipFree(c->pre_blk); (void)hipFree(c->pre_nblk); (void)hipFree(c->pre_sort);
-    (void)hipFree(c->pre_lits); (void)hipFree(c->pre_lit); (void)hipFree(c->pre_nlit);
-    if (c->st2) (void)hipStreamDestroy(c->st2);
-    (void)hipFree(c->dfl_wr); (void)hipFree(c->dfl_order); (void)hipFree(c->dfl_link); (void)hipFree(c->dfl_best); (void)hipFree(c->dfl_syms); (void)hipFree(c->dfl_meta); (void)hipFree(c->dfl_blocks);
-    (void)hipFree(c->dfl_fsyms); (void)hipFree(c->dfl_fmeta); (void)hipFree(c->dfl_fblocks); (void)hipFree(c->dfl_rank); (void)hipFree(c->dfl_state); (void)hipFree(c->dfl_maxlen);
-    if (c->dfl_seg_sync) for (int i = 0; i < 2; i++) { (void)hipStreamDestroy(c->dfl_sort_st[i]); for (int k = 0; k < 2; k++) { (void)hipEventDestroy(c->dfl_sorted[i][k]); (void)hipEventDestroy(c->dfl_parsed[i][k]); } }
-    if (c->dfl_events) for (int i = 0; i < 2; i++) { (void)hipEventDestroy(c->dfl_searched[i]); (void)hipEventDestroy(c->dfl_done[i]); }
     delete c;
 }
 
@@ -546,48 +527,40 @@ extern "C" int kmp_batch_memory(kmp_batch_ctx* c, kmp_batch_memory_info* info)
 {
     if (!c || !info || info->struct_bytes < sizeof(kmp_batch_memory_info)) { g_last_error = "kmp_batch_memory: bad argument"; return KMP_ERR_ARG; }
     size_t const ns = c->max_slices;
-    kmp_batch_memory_info m; memset(&m, 0, sizeof m); m.struct_bytes = sizeof m;
-    size_t const tbytes = (size_t)c->nteams * KX_TBL_ENTRIES * sizeof(u32);
-    if (c->arena) { m.arena = c->arena_bytes; m.arena_used = tbytes + ns * c->seq_cap * sizeof(KSeq) + ns * c->lit_cap + ns * sizeof(KSliceMeta) + ns * c->scratch_words * sizeof(u32); }
-    else { m.arena = 0; m.arena_used = 0; m.workspace = tbytes + ns * c->seq_cap * sizeof(KSeq) + ns * c->lit_cap + ns * sizeof(KSliceMeta) + ns * c->scratch_words * sizeof(u32); }
-    m.workspace += (size_t)c->nteams * sizeof(u32) + ns * sizeof(u32) + 192;
-    if (c->tables_flat) m.other_tables += tbytes + (size_t)c->nteams * sizeof(u32);
-    if (c->tables4) m.other_tables += (size_t)c->teams4 * KX_TBL4_ENTRIES * sizeof(u32) + (size_t)c->teams4 * sizeof(u32);
-    if (c->big_tables4) m.other_tables += ns * KX_BIG4_ENTRIES * sizeof(u32);
-    if (c->d_dict) m.other_tables += c->dict_size + 64 + ((size_t)4 << c->cdH) + ((size_t)4 << c->cdC);
-    if (c->lz_srt) m.other_tables += (size_t)c->lz_chunk * c->lz_pos_cap * (sizeof(KLazyRec) + sizeof(u32));       // (levels 5 .. 10: the sorted positions' records and where each stands)
-    if (c->big) m.block_chain = ns * sizeof(KFrameState) + ns * 512 * sizeof(u32) + ns * KX_BIG_TBL_ENTRIES * sizeof(u32) + ns * 4 + 64;
-    if (c->pre_stage) m.decode_staging += (size_t)c->pre_slices * c->pre_seq_cap * 8u + (size_t)c->pre_slices * c->pre_blk_cap * sizeof(KPreBlk) + (size_t)c->pre_slices * 4u + ((size_t)c->pre_slices * 2u + KXP_SORT_BUCKETS) * 4u;
-    if (c->pre_lits) m.decode_staging += (size_t)c->pre_slices * c->pre_lit_cap + (size_t)c->pre_slices * c->pre_blk_cap * sizeof(KPreLit) + (size_t)c->pre_slices * 4u;
-    if (c->dfl_link) {
-        size_t const span = c->dfl_pos_cap > 65536u ? 65536u : c->dfl_pos_cap;          // (above 64 KiB the search arrays hold one 64 KiB span per slice: kmp_deflate.hip)
-        m.deflate_workspace += (size_t)2 * c->dfl_chunk * (span * ((c->dfl_rank ? 2u : 1u) * (sizeof(u16) + sizeof(KdBest) * 2u + sizeof(u32)) + (c->dfl_rank ? sizeof(u16) : 0)) + (size_t)c->dfl_pos_cap * sizeof(u32)
-                                                            + sizeof(KdSliceMeta) + (size_t)c->dfl_blk_cap * sizeof(KdBlockInfo));
-    }
-    if (c->dfl_fsyms) m.deflate_workspace += (size_t)4 * c->dfl_chunk * ((size_t)c->dfl_pos_cap * sizeof(u32) + sizeof(KdSliceMeta) + (size_t)c->dfl_blk_cap * sizeof(KdBlockInfo));
+    kmp_batch_memory_info m = {}; m.struct_bytes = sizeof m;
+    m.arena = c->arena.bytes;
+    if (c->arena) m.arena_used = (size_t)c->nteams * KX_TBL_ENTRIES * sizeof(u32) + ns * c->seq_cap * sizeof(KSeq) + ns * c->lit_cap + ns * sizeof(KSliceMeta) + ns * c->scratch_words * sizeof(u32);
+    m.workspace = c->seqs_buf.bytes + c->lits_buf.bytes + c->meta_buf.bytes + c->scratch_buf.bytes + c->tables_buf.bytes
+                + c->team_epoch.bytes + c->counter.bytes + c->len_ok.bytes + c->d_status.bytes;
+    m.other_tables = part_bytes(c->flat) + part_bytes(c->t4) + part_bytes(c->chain_t4) + part_bytes(c->dict) + part_bytes(c->ddict) + part_bytes(c->lz);
+    m.block_chain = c->fstate.bytes + c->hufct.bytes + c->big_tables.bytes + c->remaining.bytes + c->big_counters.bytes;
+    m.decode_staging = part_bytes(c->pre_seq) + part_bytes(c->pre_lit);
+    m.deflate_workspace = part_bytes(c->dfl) + part_bytes(c->dflf);
     m.total = m.arena + m.workspace + m.other_tables + m.block_chain + m.decode_staging + m.deflate_workspace;
     *info = m;
     return KMP_OK;
 }
 
 extern "C" int kmp_batch_set_profiling(kmp_batch_ctx* c, int on) { if (!c) return KMP_ERR_ARG; c->profiling = on; return KMP_OK; }
+// 0 / 1: mean duration of the k_zstd_match / k_zstd_entropy launches of the last timed level-3 batch; 2: decode; 3: DEFLATE
 extern "C" int kmp_batch_last_kernel_ms(kmp_batch_ctx* c, int which, float* ms)
 {
-    if (!c || which < 0 || which > 6 || !ms || !c->ev_valid[which]) { g_last_error = "no timing recorded"; return KMP_ERR_ARG; }
+    int const timed = !c || !ms ? 0 : which == 0 || which == 1 ? c->zstd_timed : which == 2 ? c->decode_timed : which == 3 ? c->deflate_timed : 0;
+    if (!timed) { g_last_error = "no timing recorded"; return KMP_ERR_ARG; }
     if (which <= 1) {
-        // zstd compress: mean duration of the k_zstd_match (0) / k_zstd_entropy (1) launches of the last batch
         float sum = 0;
-        for (u32 i = 0; i < c->last_chunks; i++) {
-            hipEvent_t* const e = which == 0 ? c->evm[i] : c->eve[i]; float t = 0;
-            HIP_TRY(hipEventSynchronize(e[1]));
-            HIP_TRY(hipEventElapsedTime(&t, e[0], e[1]));
-            sum += t;
+        for (u32 i = 0; i < c->timed_chunks; i++) {
+            kmp_span const& t = which == 0 ? c->match[i] : c->entropy[i]; float x = 0;
+            HIP_TRY(hipEventSynchronize(t.end));
+            HIP_TRY(hipEventElapsedTime(&x, t.start, t.end));
+            sum += x;
         }
-        *ms = sum / (float)c->last_chunks;
+        *ms = sum / (float)c->timed_chunks;
         return KMP_OK;
     }
-    HIP_TRY(hipEventSynchronize(c->ev[2 * which + 1]));
-    HIP_TRY(hipEventElapsedTime(ms, c->ev[2 * which], c->ev[2 * which + 1]));
+    kmp_span const& t = which == 2 ? c->decode_t : c->deflate_t;
+    HIP_TRY(hipEventSynchronize(t.end));
+    HIP_TRY(hipEventElapsedTime(ms, t.start, t.end));
     return KMP_OK;
 }
 /* random 4-byte loads per second and load + store pairs per second over this context's level-3 team tables, measured when
@@ -665,14 +638,16 @@ extern "C" size_t kmp_zstd_compress_bound(size_t n)
 static int flat_tables(kmp_batch_ctx* c, u32** tables, u32** epochs)
 {
     if (c->tseg_n == 1) { *tables = c->tables; *epochs = c->team_epoch; return KMP_OK; }
-    if (!c->tables_flat) {
+    auto fill = [c](table_part& f) {
         size_t const tbytes = (size_t)c->nteams * KX_TBL_ENTRIES * sizeof(u32);
-        int const rc = place_alloc(&c->tables_flat, tbytes, nullptr, nullptr); if (rc != KMP_OK) return rc;
-        HIP_TRY(hipMalloc((void**)&c->team_epoch_flat, (size_t)c->nteams * sizeof(u32)));
-        HIP_TRY(hipMemset(c->tables_flat, 0, tbytes));
-        HIP_TRY(hipMemset(c->team_epoch_flat, 0, (size_t)c->nteams * sizeof(u32)));
-    }
-    *tables = c->tables_flat; *epochs = c->team_epoch_flat;
+        KMP_TRY(place_alloc(f.tables, tbytes, nullptr, nullptr));
+        KMP_TRY(f.epochs.alloc((size_t)c->nteams * sizeof(u32), "hipMalloc(flat team epochs)"));
+        HIP_TRY(hipMemset(f.tables, 0, tbytes));
+        HIP_TRY(hipMemset(f.epochs, 0, (size_t)c->nteams * sizeof(u32)));
+        return KMP_OK;
+    };
+    if (!c->flat) KMP_TRY(build_part(c->flat, KMP_PART_FLAT_TABLES, fill));
+    *tables = c->flat->tables; *epochs = c->flat->epochs;
     return KMP_OK;
 }
 
@@ -704,46 +679,42 @@ static int zstd_compress_lazy(kmp_batch_ctx* c, const void* d_src, const uint64_
     e.flags = 8u | ((u32)level << 12);           // literals are gathered by the entropy kernel; the level: it derives each slice's strategy from it
     hipLaunchKernelGGL(k_zstd_entropy, dim3(n), dim3(64), 0, st, e);
     HIP_TRY(hipGetLastError());
-    c->last_chunks = 1;
+    c->last_chunks = 1; c->zstd_timed = 0;          // (no per-chunk timings: those are level 3's)
     return batch_end(c, st, d_in_len, n, c->max_slice_bytes, d_out_len, c->meta);
 }
 // need_bytes: the largest slice these kernels will parse (level 4 hands them only its slices up to 16 KiB: a quarter of the memory)
 static int lazy_workspace(kmp_batch_ctx* c, u32 need_bytes)
 {
-    if (c->lz_srt && c->lz_pos_cap < ((need_bytes + 63u) & ~63u)) {          // made for a smaller need: once more, larger
-        (void)hipFree(c->lz_srt); (void)hipFree(c->lz_wr); c->lz_srt = nullptr; c->lz_wr = nullptr;
-    }
-    if (!c->lz_srt) {
-        u32 const pos_cap = (need_bytes + 63u) & ~63u;
+    u32 const pos_cap = (need_bytes + 63u) & ~63u;
+    if (c->lz && c->lz->pos_cap < pos_cap) c->lz.reset();                  // made for a smaller need: once more, larger
+    if (c->lz) return KMP_OK;
+    auto fill = [c, pos_cap](lazy_part& z) {
         u32 cap = (u32)((1ull << 30) / pos_cap); if (cap > 16384u) cap = 16384u; if (cap < 1u) cap = 1u;
-        u32 const chunk = c->max_slices < cap ? c->max_slices : cap;
-        HIP_TRY(hipMalloc((void**)&c->lz_srt, (size_t)chunk * pos_cap * sizeof(KLazyRec)));
-        if (hipMalloc((void**)&c->lz_wr, (size_t)chunk * pos_cap * sizeof(u32)) != hipSuccess) {
-            (void)hipGetLastError(); (void)hipFree(c->lz_srt); c->lz_srt = nullptr;
-            g_last_error = "kmp_zstd_compress_batch_level: no memory for the workspace of levels 5 .. 10"; return KMP_ERR_HIP;
-        }
-        (void)hipFree(c->lz_order); c->lz_order = nullptr;
-        if (hipMalloc((void**)&c->lz_order, ((size_t)2 * chunk + 256) * sizeof(u32)) != hipSuccess) { (void)hipGetLastError(); c->lz_order = nullptr; }      // (without it the slices go as they come)
-        c->lz_pos_cap = pos_cap; c->lz_chunk = chunk;
-    }
-    return KMP_OK;
+        z.chunk = c->max_slices < cap ? c->max_slices : cap; z.pos_cap = pos_cap;
+        KMP_TRY(z.srt.alloc((size_t)z.chunk * pos_cap * sizeof(KLazyRec), "kmp_zstd_compress_batch_level: no memory for the workspace of levels 5 .. 10"));
+        KMP_TRY(z.wr.alloc((size_t)z.chunk * pos_cap * sizeof(u32), "kmp_zstd_compress_batch_level: no memory for the workspace of levels 5 .. 10"));
+        (void)z.order.alloc(((size_t)2 * z.chunk + 256) * sizeof(u32));      // (without it the slices go as they come)
+        return KMP_OK;
+    };
+    return build_part(c->lz, KMP_PART_LAZY_LEVELS, fill);
 }
 // sort + parse of the slices [first0, first0 + n) of a batch, piece by piece (the slices' sanitised lengths are c->len_ok; sequences and
 // the per-slice record go where the other parsers put theirs).  Slices the level does not parse this way at their size are skipped: at
 // level 4 their record stays what k_zstd_match left (it serves 16 KiB < size <= 128 KiB), at the other levels it says "not served".
 static int lazy_parse(kmp_batch_ctx* c, hipStream_t st, const void* d_src, const uint64_t* d_in_off, u32 n, u32 first0, int level)
 {
-    for (u32 first = first0; first < first0 + n; first += c->lz_chunk) {
-        u32 const m = (first0 + n - first < c->lz_chunk) ? first0 + n - first : c->lz_chunk;
+    lazy_part const& z = *c->lz;
+    for (u32 first = first0; first < first0 + n; first += z.chunk) {
+        u32 const m = (first0 + n - first < z.chunk) ? first0 + n - first : z.chunk;
         KLazyArgs g;
         g.src = (const u8*)d_src; g.in_off = d_in_off + first; g.in_len = c->len_ok + first; g.n_slices = m;
-        g.rec = (KLazyRec*)c->lz_srt; g.wr = c->lz_wr; g.pos_cap = c->lz_pos_cap;
+        g.rec = (KLazyRec*)z.srt.p; g.wr = z.wr; g.pos_cap = z.pos_cap;
         g.seqs = c->seqs + (size_t)first * c->seq_cap; g.seq_cap = c->seq_cap; g.meta = c->meta + first; g.level = (u32)level;
         // (the parse takes the costliest slices first: cost classes from the sort, a counting sort of the classes; batches worth ordering only)
-        u32* const ord = (m >= 1024u && c->lz_order) ? c->lz_order : nullptr;
-        if (ord) { g.order_key = ord; g.order_hist = ord + c->lz_chunk; HIP_TRY(hipMemsetAsync(g.order_hist, 0, 256 * sizeof(u32), st)); }
+        u32* const ord = (m >= 1024u && z.order) ? z.order.p : nullptr;
+        if (ord) { g.order_key = ord; g.order_hist = ord + z.chunk; HIP_TRY(hipMemsetAsync(g.order_hist, 0, 256 * sizeof(u32), st)); }
         hipLaunchKernelGGL(k_zstd_lazy_sort, dim3(m), dim3(256), 0, st, g);
-        if (ord) { KMP_TRY(size_sort_keys(c, st, m, g.order_key, g.order_hist, ord + c->lz_chunk + 256)); g.order = ord + c->lz_chunk + 256; }
+        if (ord) { KMP_TRY(size_sort_keys(c, st, m, g.order_key, g.order_hist, ord + z.chunk + 256)); g.order = ord + z.chunk + 256; }
         if (c->max_slice_bytes <= 65536u) hipLaunchKernelGGL(k_zstd_lazy<2048>, dim3(m), dim3(64), 0, st, g);
         else hipLaunchKernelGGL(k_zstd_lazy<4096>, dim3(m), dim3(64), 0, st, g);
         HIP_TRY(hipGetLastError());
@@ -789,28 +760,21 @@ extern "C" int kmp_zstd_compress_batch_level(kmp_batch_ctx* c, const void* d_src
         { u32* ft_ = nullptr; u32* fe_ = nullptr; KMP_TRY(flat_tables(c, &ft_, &fe_)); g.m.tables = ft_; g.m.tseg_n = 1; g.m.team_epoch = fe_; } g.m.counter = c->counter + ci; g.m.flags = 6; g.m.fstate = nullptr; g.m.big_tables = nullptr;
         g.level = neg ? 0u : (u32)level; g.step0 = neg ? (u32)(1 - level) : 2u;
         u32 blocks = (m_n + tpw - 1) / tpw; if (blocks > c->match_blocks) blocks = c->match_blocks;
-        switch (c->G) {
-        case 2:  hipLaunchKernelGGL(k_zstd_match_fast<2>, dim3(blocks), dim3(64), 0, st, g); break;
-        case 4:  hipLaunchKernelGGL(k_zstd_match_fast<4>, dim3(blocks), dim3(64), 0, st, g); break;
-        case 8:  hipLaunchKernelGGL(k_zstd_match_fast<8>, dim3(blocks), dim3(64), 0, st, g); break;
-        case 16: hipLaunchKernelGGL(k_zstd_match_fast<16>, dim3(blocks), dim3(64), 0, st, g); break;
-        case 32: hipLaunchKernelGGL(k_zstd_match_fast<32>, dim3(blocks), dim3(64), 0, st, g); break;
-        default: hipLaunchKernelGGL(k_zstd_match_fast<64>, dim3(blocks), dim3(64), 0, st, g); break;
-        }
+        by_team_width(c->G, [&](auto w) { hipLaunchKernelGGL(k_zstd_match_fast<decltype(w)::value>, dim3(blocks), dim3(64), 0, st, g); });
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(c->evm[ci][1], st));
+        HIP_TRY(hipEventRecord(c->match[ci].end, st));
         KEntropyArgs e;
         e.src = (const u8*)d_src; e.in_off = d_in_off + first; e.in_len = c->len_ok + first; e.n_slices = m_n;
         e.seqs = g.m.seqs; e.seq_cap = c->seq_cap; e.lits = g.m.lits; e.lit_cap = c->lit_cap; e.meta = g.m.meta;
         e.scratch = c->scratch + (size_t)first * c->scratch_words; e.scratch_words = c->scratch_words;
         e.dst = (u8*)d_dst; e.out_off = d_out_off + first; e.out_len = d_out_len + first; e.flags = 8u | 32u | (neg ? 64u : 0u);   // gather literals; strategy "fast"; negative levels: literals stay raw
         hipStream_t es = st;
-        if (ci + 1 < chunks) { es = c->st2; HIP_TRY(hipStreamWaitEvent(es, c->evm[ci][1], 0)); forked = true; }
+        if (ci + 1 < chunks) { es = c->st2; HIP_TRY(hipStreamWaitEvent(es, c->match[ci].end, 0)); forked = true; }
         hipLaunchKernelGGL(k_zstd_entropy, dim3(m_n), dim3(64), 0, es, e);
         HIP_TRY(hipGetLastError());
     }
     if (forked) { HIP_TRY(hipEventRecord(c->ev_join, c->st2)); HIP_TRY(hipStreamWaitEvent(st, c->ev_join, 0)); }
-    c->last_chunks = chunks;
+    c->last_chunks = chunks; c->zstd_timed = 0;
     return batch_end(c, st, d_in_len, n, c->max_slice_bytes, d_out_len, c->meta);
 }
 
@@ -836,7 +800,7 @@ extern "C" int kmp_zstd_compress_batch_dict(kmp_batch_ctx* c, const void* d_src,
     HIP_TRY(hipSetDevice(c->device));
     // (re)build the CDict when the dictionary changed
     u64 hsh = 1469598103934665603ull; for (u32 i = 0; i < dict_size; i++) { hsh ^= ((const u8*)h_dict)[i]; hsh *= 1099511628211ull; }
-    if (!c->d_dict || c->dict_size != dict_size || c->dict_hash != hsh) {
+    if (!c->dict || c->dict->size != dict_size || c->dict->hash != hsh) {
         // A dictionary in zstd's own format (magic EC30A437) is loaded as libzstd loads it: entropy tables and repeat offsets for the first
         // block (KDictPrior), the bytes behind them as the content matches are searched in; anything else is content from its first byte.
         KDictPrior prior; size_t content_off = 0;
@@ -844,52 +808,50 @@ extern "C" int kmp_zstd_compress_batch_dict(kmp_batch_ctx* c, const void* d_src,
         if (formatted < 0) { g_last_error = "kmp_zstd_compress_batch_dict: the dictionary starts with zstd's dictionary magic but its header is damaged (libzstd: Dictionary is corrupted)"; return KMP_ERR_ARG; }
         const u8* const content = (const u8*)h_dict + content_off; u32 const content_size = dict_size - (u32)content_off;
         HIP_TRY(hipStreamSynchronize(st));
-        (void)hipFree(c->d_dict); (void)hipFree(c->d_dictL); (void)hipFree(c->d_dictS); (void)hipFree(c->d_prior); c->d_dict = nullptr; c->d_dictL = nullptr; c->d_dictS = nullptr; c->d_prior = nullptr;
-        cdict_params(dict_size, &c->cdW, &c->cdC, &c->cdH, &c->cdM);        // (libzstd sizes the CDict and the frame's window by the whole dictionary, header included)
-        std::vector<u32> tl, ts;
-        cdict_fill(tl, c->cdH, ts, c->cdC, c->cdM, content, content_size);
-        HIP_TRY(hipMalloc((void**)&c->d_dict, content_size + 64));
-        HIP_TRY(hipMalloc((void**)&c->d_dictL, tl.size() * 4)); HIP_TRY(hipMalloc((void**)&c->d_dictS, ts.size() * 4));
-        HIP_TRY(hipMemcpy(c->d_dict, content, content_size, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(c->d_dictL, tl.data(), tl.size() * 4, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(c->d_dictS, ts.data(), ts.size() * 4, hipMemcpyHostToDevice));
-        if (formatted) {
-            HIP_TRY(hipMalloc((void**)&c->d_prior, sizeof(KDictPrior)));
-            HIP_TRY(hipMemcpy(c->d_prior, &prior, sizeof(KDictPrior), hipMemcpyHostToDevice));
-            c->dict_rep[0] = prior.rep[0]; c->dict_rep[1] = prior.rep[1];
-        } else { c->dict_rep[0] = 1; c->dict_rep[1] = 4; }
-        c->dict_content = content_size;
-        c->dict_size = dict_size; c->dict_hash = hsh;
+        c->dict.reset();
+        auto fill = [&](dict_part& d) {
+            cdict_params(dict_size, &d.W, &d.C, &d.H, &d.M);        // (libzstd sizes the CDict and the frame's window by the whole dictionary, header included)
+            std::vector<u32> tl, ts;
+            cdict_fill(tl, d.H, ts, d.C, d.M, content, content_size);
+            KMP_TRY(d.content.alloc(content_size + 64, "hipMalloc(dictionary)"));
+            KMP_TRY(d.L.alloc(tl.size() * 4, "hipMalloc(dictionary tables)")); KMP_TRY(d.S.alloc(ts.size() * 4, "hipMalloc(dictionary tables)"));
+            HIP_TRY(hipMemcpy(d.content, content, content_size, hipMemcpyHostToDevice));
+            HIP_TRY(hipMemcpy(d.L, tl.data(), tl.size() * 4, hipMemcpyHostToDevice));
+            HIP_TRY(hipMemcpy(d.S, ts.data(), ts.size() * 4, hipMemcpyHostToDevice));
+            if (formatted) {
+                KMP_TRY(d.prior.alloc(sizeof(KDictPrior), "hipMalloc(dictionary entropy tables)"));
+                HIP_TRY(hipMemcpy(d.prior, &prior, sizeof(KDictPrior), hipMemcpyHostToDevice));
+                d.rep[0] = prior.rep[0]; d.rep[1] = prior.rep[1];
+            } else { d.rep[0] = 1; d.rep[1] = 4; }
+            d.content_size = content_size;
+            d.size = dict_size; d.hash = hsh;
+            return KMP_OK;
+        };
+        KMP_TRY(build_part(c->dict, KMP_PART_DICT, fill));
     }
+    dict_part const& dp = *c->dict;
     KMP_TRY(batch_begin(c, st, d_in_len, n, c->max_slice_bytes));
     HIP_TRY(hipMemsetAsync(c->counter, 0, 4, st));
     KDictArgs g;
     g.m.src = (const u8*)d_src; g.m.in_off = d_in_off; g.m.in_len = c->len_ok; g.m.n_slices = n;
     g.m.seqs = c->seqs; g.m.seq_cap = c->seq_cap; g.m.lits = c->lits; g.m.lit_cap = c->lit_cap; g.m.meta = c->meta;
     { u32* ft_ = nullptr; u32* fe_ = nullptr; KMP_TRY(flat_tables(c, &ft_, &fe_)); g.m.tables = ft_; g.m.tseg_n = 1; g.m.team_epoch = fe_; } g.m.counter = c->counter; g.m.flags = 6; g.m.fstate = nullptr; g.m.big_tables = nullptr;
-    g.dict = c->d_dict; g.dict_size = c->dict_content; g.dictL = c->d_dictL; g.dictS = c->d_dictS; g.rep0 = c->dict_rep[0]; g.rep1 = c->dict_rep[1];
-    g.dWindowLog = c->cdW; g.dHashLog = c->cdH; g.dChainLog = c->cdC; g.dMinMatch = c->cdM;
+    g.dict = dp.content; g.dict_size = dp.content_size; g.dictL = dp.L; g.dictS = dp.S; g.rep0 = dp.rep[0]; g.rep1 = dp.rep[1];
+    g.dWindowLog = dp.W; g.dHashLog = dp.H; g.dChainLog = dp.C; g.dMinMatch = dp.M;
     u32 const tpw = 64 / (u32)c->G;
     u32 blocks = (n + tpw - 1) / tpw; if (blocks > c->match_blocks) blocks = c->match_blocks;
-    switch (c->G) {
-    case 2:  hipLaunchKernelGGL(k_zstd_match_dict<2>, dim3(blocks), dim3(64), 0, st, g); break;
-    case 4:  hipLaunchKernelGGL(k_zstd_match_dict<4>, dim3(blocks), dim3(64), 0, st, g); break;
-    case 8:  hipLaunchKernelGGL(k_zstd_match_dict<8>, dim3(blocks), dim3(64), 0, st, g); break;
-    case 16: hipLaunchKernelGGL(k_zstd_match_dict<16>, dim3(blocks), dim3(64), 0, st, g); break;
-    case 32: hipLaunchKernelGGL(k_zstd_match_dict<32>, dim3(blocks), dim3(64), 0, st, g); break;
-    default: hipLaunchKernelGGL(k_zstd_match_dict<64>, dim3(blocks), dim3(64), 0, st, g); break;
-    }
+    by_team_width(c->G, [&](auto w) { hipLaunchKernelGGL(k_zstd_match_dict<decltype(w)::value>, dim3(blocks), dim3(64), 0, st, g); });
     HIP_TRY(hipGetLastError());
     KEntropyArgs e;
     e.src = (const u8*)d_src; e.in_off = d_in_off; e.in_len = c->len_ok; e.n_slices = n;
     e.seqs = c->seqs; e.seq_cap = c->seq_cap; e.lits = c->lits; e.lit_cap = c->lit_cap; e.meta = c->meta;
     e.scratch = c->scratch; e.scratch_words = c->scratch_words;
     e.dst = (u8*)d_dst; e.out_off = d_out_off; e.out_len = d_out_len; e.flags = 8u;       // literals are gathered by the entropy kernel
-    e.prior = c->d_prior;
-    if (c->d_prior) hipLaunchKernelGGL(k_zstd_entropy_prior, dim3(n), dim3(64), 0, st, e);
+    e.prior = dp.prior;
+    if (dp.prior) hipLaunchKernelGGL(k_zstd_entropy_prior, dim3(n), dim3(64), 0, st, e);
     else hipLaunchKernelGGL(k_zstd_entropy, dim3(n), dim3(64), 0, st, e);
     HIP_TRY(hipGetLastError());
-    c->last_chunks = 1;
+    c->last_chunks = 1; c->zstd_timed = 0;
     return batch_end(c, st, d_in_len, n, c->max_slice_bytes, d_out_len, c->meta);
 }
 
@@ -907,10 +869,9 @@ int zstd_compress_big(kmp_batch_ctx* c, const void* d_src, const uint64_t* d_in_
     if (level4) {
         // level 4's double-fast rows on this path (16 - 128 KiB: hash 17 / chain 17; above 256 KiB and streams: 18 / 18): per-slice tables of
         // 2 MiB, allocated by the first such batch of the context
-        if (!c->big_tables4 && hipMalloc((void**)&c->big_tables4, (size_t)c->max_slices * KX_BIG4_ENTRIES * sizeof(u32)) != hipSuccess) {
-            (void)hipGetLastError(); c->big_tables4 = nullptr; g_last_error = "kmp_zstd_compress_batch_level: no memory for level 4's tables"; return KMP_ERR_HIP;
-        }
-        HIP_TRY(hipMemsetAsync(c->big_tables4, 0, (size_t)n * KX_BIG4_ENTRIES * sizeof(u32), st));
+        auto fill = [c](table_part& t) { return t.tables.alloc((size_t)c->max_slices * KX_BIG4_ENTRIES * sizeof(u32), "kmp_zstd_compress_batch_level: no memory for level 4's tables"); };
+        if (!c->chain_t4) KMP_TRY(build_part(c->chain_t4, KMP_PART_CHAIN_TABLES4, fill));
+        HIP_TRY(hipMemsetAsync(c->chain_t4->tables, 0, (size_t)n * KX_BIG4_ENTRIES * sizeof(u32), st));
     } else
     HIP_TRY(hipMemsetAsync(c->big_tables, 0, (size_t)n * KX_BIG_TBL_ENTRIES * sizeof(u32), st));
     HIP_TRY(hipMemsetAsync(c->remaining, 0, 4, st));
@@ -924,7 +885,7 @@ int zstd_compress_big(kmp_batch_ctx* c, const void* d_src, const uint64_t* d_in_
     m.tables = c->tables; for (int ts_ = 0; ts_ < 4; ts_++) m.tseg[ts_] = c->tseg[ts_]; m.tseg_n = c->tseg_n; m.team_epoch = c->team_epoch; m.counter = c->counter;
     m.flags = 2u | (streaming ? 8u : 0u) | (c->max_slice_bytes >= KX_BLK_WIDE_FROM ? 16u : 0u);
     m.fstate = c->fstate; m.big_tables = c->big_tables;
-    if (level4) { m.level = 4; m.big_tables = c->big_tables4; m.big_stride = KX_BIG4_ENTRIES; m.big_long = KX_BIG4_LONG; }
+    if (level4) { m.level = 4; m.big_tables = c->chain_t4->tables; m.big_stride = KX_BIG4_ENTRIES; m.big_long = KX_BIG4_LONG; }
     KFrameArgs e;
     e.src = (const u8*)d_src; e.in_off = d_in_off; e.in_len = d_in_len; e.n_slices = n;
     e.seqs = c->seqs; e.seq_cap = c->seq_cap; e.lits = c->lits; e.lit_cap = c->lit_cap; e.meta = c->meta;
@@ -958,36 +919,15 @@ int zstd_compress_big(kmp_batch_ctx* c, const void* d_src, const uint64_t* d_in_
         if (level2 && !streaming) {
             // level 2, sizes known: the slices of its double-fast row first (class 1), the others (class 2) through the fast parser below
             g.e.strategy = 0; g.e.cls = 1; g.m.flags = m.flags | 32u | (1u << 6);
-            switch (bigG) {
-            case 2:  hipLaunchKernelGGL(k_zstd_big<2>, dim3(grid), dim3(64), 0, st, g); break;
-            case 4:  hipLaunchKernelGGL(k_zstd_big<4>, dim3(grid), dim3(64), 0, st, g); break;
-            case 8:  hipLaunchKernelGGL(k_zstd_big<8>, dim3(grid), dim3(64), 0, st, g); break;
-            case 16: hipLaunchKernelGGL(k_zstd_big<16>, dim3(grid), dim3(64), 0, st, g); break;
-            case 32: hipLaunchKernelGGL(k_zstd_big<32>, dim3(grid), dim3(64), 0, st, g); break;
-            default: hipLaunchKernelGGL(k_zstd_big<64>, dim3(grid), dim3(64), 0, st, g); break;
-            }
+            by_team_width(bigG, [&](auto w) { hipLaunchKernelGGL(k_zstd_big<decltype(w)::value>, dim3(grid), dim3(64), 0, st, g); });
             HIP_TRY(hipGetLastError());
             HIP_TRY(hipMemsetAsync(c->big_counters, 0, (size_t)n * 4, st));
             g.e.strategy = 1; g.e.cls = 2; g.m.flags = m.flags | (2u << 6);
         }
-        if (strategy) switch (bigG) {
-        case 2:  hipLaunchKernelGGL(k_zstd_big_fast<2>, dim3(grid), dim3(64), 0, st, g); break;
-        case 4:  hipLaunchKernelGGL(k_zstd_big_fast<4>, dim3(grid), dim3(64), 0, st, g); break;
-        case 8:  hipLaunchKernelGGL(k_zstd_big_fast<8>, dim3(grid), dim3(64), 0, st, g); break;
-        case 16: hipLaunchKernelGGL(k_zstd_big_fast<16>, dim3(grid), dim3(64), 0, st, g); break;
-        case 32: hipLaunchKernelGGL(k_zstd_big_fast<32>, dim3(grid), dim3(64), 0, st, g); break;
-        default: hipLaunchKernelGGL(k_zstd_big_fast<64>, dim3(grid), dim3(64), 0, st, g); break;
-        }
-        else switch (bigG) {
-        case 2:  hipLaunchKernelGGL(k_zstd_big<2>, dim3(grid), dim3(64), 0, st, g); break;
-        case 4:  hipLaunchKernelGGL(k_zstd_big<4>, dim3(grid), dim3(64), 0, st, g); break;
-        case 8:  hipLaunchKernelGGL(k_zstd_big<8>, dim3(grid), dim3(64), 0, st, g); break;
-        case 16: hipLaunchKernelGGL(k_zstd_big<16>, dim3(grid), dim3(64), 0, st, g); break;
-        case 32: hipLaunchKernelGGL(k_zstd_big<32>, dim3(grid), dim3(64), 0, st, g); break;
-        default: hipLaunchKernelGGL(k_zstd_big<64>, dim3(grid), dim3(64), 0, st, g); break;
-        }
+        if (strategy) by_team_width(bigG, [&](auto w) { hipLaunchKernelGGL(k_zstd_big_fast<decltype(w)::value>, dim3(grid), dim3(64), 0, st, g); });
+        else by_team_width(bigG, [&](auto w) { hipLaunchKernelGGL(k_zstd_big<decltype(w)::value>, dim3(grid), dim3(64), 0, st, g); });
         HIP_TRY(hipGetLastError());
-        c->last_rounds = 0; c->last_chunks = 1;
+        c->last_rounds = 0; c->last_chunks = 1; c->zstd_timed = 0;
         return batch_end(c, st, d_in_len_caller, n, c->max_slice_bytes, d_out_len, nullptr);
     }
 #ifdef KMP_ABLATIONS
@@ -1003,19 +943,12 @@ int zstd_compress_big(kmp_batch_ctx* c, const void* d_src, const uint64_t* d_in_
         if (left == 0) break;
         if (++rounds > KMP_MAX_BIG_SLICE_BYTES / 64u) { g_last_error = "kmp_zstd_compress_batch: block rounds did not finish"; return KMP_ERR_KERNEL; }
         HIP_TRY(hipMemsetAsync(c->counter, 0, 8, st));
-        switch (bigR) {
-        case 2:  hipLaunchKernelGGL(k_zstd_match_blk<2>, dim3(blocks), dim3(64), 0, st, m); break;
-        case 4:  hipLaunchKernelGGL(k_zstd_match_blk<4>, dim3(blocks), dim3(64), 0, st, m); break;
-        case 8:  hipLaunchKernelGGL(k_zstd_match_blk<8>, dim3(blocks), dim3(64), 0, st, m); break;
-        case 16: hipLaunchKernelGGL(k_zstd_match_blk<16>, dim3(blocks), dim3(64), 0, st, m); break;
-        case 32: hipLaunchKernelGGL(k_zstd_match_blk<32>, dim3(blocks), dim3(64), 0, st, m); break;
-        default: hipLaunchKernelGGL(k_zstd_match_blk<64>, dim3(blocks), dim3(64), 0, st, m); break;
-        }
+        by_team_width(bigR, [&](auto w) { hipLaunchKernelGGL(k_zstd_match_blk<decltype(w)::value>, dim3(blocks), dim3(64), 0, st, m); });
         HIP_TRY(hipGetLastError());
         hipLaunchKernelGGL(k_zstd_frame, dim3(n), dim3(64), 0, st, e);
         HIP_TRY(hipGetLastError());
     }
-    c->last_rounds = rounds; c->last_chunks = 1;
+    c->last_rounds = rounds; c->last_chunks = 1; c->zstd_timed = 0;
     return batch_end(c, st, d_in_len_caller, n, c->max_slice_bytes, d_out_len, nullptr);
 #else
     g_last_error = "zstd_compress_big: unreachable"; return KMP_ERR_ARG;
@@ -1067,7 +1000,7 @@ extern "C" int kmp_batch_last_rounds(kmp_batch_ctx* c) { return c ? (int)c->last
 // batch's slices go through them by the work counter).
 static int ensure_tables4(kmp_batch_ctx* c)
 {
-    if (c->tables4) return KMP_OK;
+    if (c->t4) return KMP_OK;
     // as many teams as level 3 has (65 536 x 64 KiB: 19.4 GB/s with 65 536 teams = 64 GiB of tables, 15.9 with 32 768, 14.6 with 16 384:
     // tools/r03_l4.sh), fewer when the device has less room (16 GiB stay free); KMP_L4_TEAMS caps it (the tests run many slices
     // through few teams)
@@ -1076,14 +1009,14 @@ static int ensure_tables4(kmp_batch_ctx* c)
     { size_t fr = 0, tot = 0; if (hipMemGetInfo(&fr, &tot) == hipSuccess) { size_t const room = fr > ((size_t)16 << 30) ? (fr - ((size_t)16 << 30)) / ((size_t)KX_TBL4_ENTRIES * sizeof(u32)) : 0; if (teams > room) teams = (u32)room; } else (void)hipGetLastError(); }
     teams &= ~63u; if (teams == 0) teams = 64;
     size_t const bytes = (size_t)teams * KX_TBL4_ENTRIES * sizeof(u32);
-    u32* t = nullptr; u32* e = nullptr;
-    if (hipMalloc((void**)&t, bytes) != hipSuccess || hipMalloc((void**)&e, (size_t)teams * sizeof(u32)) != hipSuccess) {
-        (void)hipGetLastError(); (void)hipFree(t); (void)hipFree(e);
-        g_last_error = "kmp_zstd_compress_batch_level: no memory for level 4's tables"; return KMP_ERR_HIP;
-    }
-    if (hipMemset(t, 0, bytes) != hipSuccess || hipMemset(e, 0, (size_t)teams * sizeof(u32)) != hipSuccess) { (void)hipGetLastError(); (void)hipFree(t); (void)hipFree(e); g_last_error = "kmp_zstd_compress_batch_level: hipMemset failed"; return KMP_ERR_HIP; }
-    c->tables4 = t; c->epoch4 = e; c->teams4 = teams;
-    return KMP_OK;
+    auto fill = [bytes, teams](table_part& t) {
+        KMP_TRY(t.tables.alloc(bytes, "kmp_zstd_compress_batch_level: no memory for level 4's tables"));
+        KMP_TRY(t.epochs.alloc((size_t)teams * sizeof(u32), "kmp_zstd_compress_batch_level: no memory for level 4's tables"));
+        if (hipMemset(t.tables, 0, bytes) != hipSuccess || hipMemset(t.epochs, 0, (size_t)teams * sizeof(u32)) != hipSuccess) { (void)hipGetLastError(); g_last_error = "kmp_zstd_compress_batch_level: hipMemset failed"; return KMP_ERR_HIP; }
+        t.teams = teams;
+        return KMP_OK;
+    };
+    return build_part(c->t4, KMP_PART_TABLES4, fill);
 }
 
 static int zstd_compress_dfast(kmp_batch_ctx* c, const void* d_src, const uint64_t* d_in_off, const uint32_t* d_in_len,
@@ -1108,7 +1041,7 @@ static int zstd_compress_dfast(kmp_batch_ctx* c, const void* d_src, const uint64
         if (c->tune_pending) {                       // the previous such batch was a trial: its whole-step time
             c->tune_pending = 0;
             float ms = 0;
-            if (hipEventSynchronize(c->tune_ev[1]) == hipSuccess && hipEventElapsedTime(&ms, c->tune_ev[0], c->tune_ev[1]) == hipSuccess) c->tune_ms[c->tune_state++] = ms;
+            if (hipEventSynchronize(c->tune.end) == hipSuccess && hipEventElapsedTime(&ms, c->tune.start, c->tune.end) == hipSuccess) c->tune_ms[c->tune_state++] = ms;
             else { (void)hipGetLastError(); c->tune_state = 2; c->tune_pick = 0; }
             if (c->tune_state == 2 && c->tune_ms[1] > 0) c->tune_pick = c->tune_ms[1] < c->tune_ms[0] ? 1u : 0u;
         }
@@ -1119,7 +1052,7 @@ static int zstd_compress_dfast(kmp_batch_ctx* c, const void* d_src, const uint64
     // batch queued on another stream waits for the last kernel of the previous one.  (Letting the next batch's match
     // kernel start beside this batch's last entropy launch was measured and gave nothing: DESIGN.md section 8.)
     KMP_TRY(batch_begin(c, st, d_in_len, n, c->max_slice_bytes));
-    if (tunable && c->tune_state < 2) HIP_TRY(hipEventRecord(c->tune_ev[0], st));
+    if (tunable && c->tune_state < 2) HIP_TRY(hipEventRecord(c->tune.start, st));
     HIP_TRY(hipMemsetAsync(c->counter, 0, 4 * KMP_MAX_CHUNKS, st));
     // Team width per batch: a small batch is bound by each slice's own chain, not by the memory system, and 8 lanes per slice
     // (7 positions per step) run it a quarter faster than 4 (64 slices: 29 ms against 39; 4 096: 43 against 49; 16 384 and up: 4
@@ -1144,11 +1077,11 @@ static int zstd_compress_dfast(kmp_batch_ctx* c, const void* d_src, const uint64
         m.tables = c->tables; for (int ts_ = 0; ts_ < 4; ts_++) m.tseg[ts_] = c->tseg[ts_]; m.tseg_n = c->tseg_n; m.team_epoch = c->team_epoch; m.counter = c->counter + ci; m.flags = match_flags;
         u32 max_blocks = (u32)((u64)c->match_blocks_l3 * (64u / (u32)c->G) / tpw);      // the context's team slots at this batch's width
         if (l4) {
-            m.tables = c->tables4; m.tseg_n = 1; m.team_epoch = c->epoch4; m.tbl_stride = KX_TBL4_ENTRIES; m.tbl_long = KX_TBL4_LONG; m.level = 4;
-            if (max_blocks > c->teams4 / tpw) max_blocks = c->teams4 / tpw;
+            m.tables = c->t4->tables; m.tseg_n = 1; m.team_epoch = c->t4->epochs; m.tbl_stride = KX_TBL4_ENTRIES; m.tbl_long = KX_TBL4_LONG; m.level = 4;
+            if (max_blocks > c->t4->teams / tpw) max_blocks = c->t4->teams / tpw;
         }
         u32 blocks = (m_n + tpw - 1) / tpw; if (blocks > max_blocks) blocks = max_blocks;
-        if (c->profiling) HIP_TRY(hipEventRecord(c->evm[ci][0], st));
+        if (c->profiling) HIP_TRY(hipEventRecord(c->match[ci].start, st));
         KEntropyArgs e;
         e.src = (const u8*)d_src; e.in_off = d_in_off + first; e.in_len = c->len_ok + first; e.n_slices = m_n;
         e.seqs = m.seqs; e.seq_cap = c->seq_cap; e.lits = c->lits + (size_t)first * c->lit_cap; e.lit_cap = c->lit_cap; e.meta = m.meta;
@@ -1173,14 +1106,7 @@ static int zstd_compress_dfast(kmp_batch_ctx* c, const void* d_src, const uint64
 #else
         bool const fuse = false;
 #endif
-        switch (G) {
-        case 2:  hipLaunchKernelGGL(k_zstd_match<2>, dim3(blocks), dim3(64), 0, st, m); break;
-        case 4:  hipLaunchKernelGGL(k_zstd_match<4>, dim3(blocks), dim3(64), 0, st, m); break;
-        case 8:  hipLaunchKernelGGL(k_zstd_match<8>, dim3(blocks), dim3(64), 0, st, m); break;
-        case 16: hipLaunchKernelGGL(k_zstd_match<16>, dim3(blocks), dim3(64), 0, st, m); break;
-        case 32: hipLaunchKernelGGL(k_zstd_match<32>, dim3(blocks), dim3(64), 0, st, m); break;
-        default: hipLaunchKernelGGL(k_zstd_match<64>, dim3(blocks), dim3(64), 0, st, m); break;
-        }
+        by_team_width(G, [&](auto w) { hipLaunchKernelGGL(k_zstd_match<decltype(w)::value>, dim3(blocks), dim3(64), 0, st, m); });
         HIP_TRY(hipGetLastError());
         if (l4) {
             // level 4 up to 16 KiB is strategy "greedy" (ZSTD_getCParams(4, n <= 16 KiB)): those slices, which k_zstd_match has passed over, are
@@ -1188,19 +1114,19 @@ static int zstd_compress_dfast(kmp_batch_ctx* c, const void* d_src, const uint64
             KMP_TRY(lazy_workspace(c, c->max_slice_bytes < 16384u ? c->max_slice_bytes : 16384u));
             KMP_TRY(lazy_parse(c, st, d_src, d_in_off, m_n, first, 4));
         }
-        HIP_TRY(hipEventRecord(c->evm[ci][1], st));
+        HIP_TRY(hipEventRecord(c->match[ci].end, st));
         e.flags = c->knob.entropy_flags | ((m.flags & 4u) ? 8u : 0u) | (l4 ? (4u << 12) : 0u);
         hipStream_t es = st;
-        if (ci + 1 < chunks) { es = c->st2; HIP_TRY(hipStreamWaitEvent(es, c->evm[ci][1], 0)); forked = true; }
-        if (c->profiling) HIP_TRY(hipEventRecord(c->eve[ci][0], es));
+        if (ci + 1 < chunks) { es = c->st2; HIP_TRY(hipStreamWaitEvent(es, c->match[ci].end, 0)); forked = true; }
+        if (c->profiling) HIP_TRY(hipEventRecord(c->entropy[ci].start, es));
         if (!fuse) hipLaunchKernelGGL(k_zstd_entropy, dim3(m_n), dim3(64), entropy_pad, es, e);
         HIP_TRY(hipGetLastError());
-        if (c->profiling) HIP_TRY(hipEventRecord(c->eve[ci][1], es));
+        if (c->profiling) HIP_TRY(hipEventRecord(c->entropy[ci].end, es));
     }
     if (forked) { HIP_TRY(hipEventRecord(c->ev_join, c->st2)); HIP_TRY(hipStreamWaitEvent(st, c->ev_join, 0)); }
     c->last_chunks = chunks;
-    if (c->profiling) { c->ev_valid[0] = 1; c->ev_valid[1] = 1; }
-    if (tunable && c->tune_state < 2) { HIP_TRY(hipEventRecord(c->tune_ev[1], st)); c->tune_pending = 1; }
+    c->zstd_timed = c->profiling; c->timed_chunks = chunks;
+    if (tunable && c->tune_state < 2) { HIP_TRY(hipEventRecord(c->tune.end, st)); c->tune_pending = 1; }
     return batch_end(c, st, d_in_len, n, c->max_slice_bytes, d_out_len, c->meta);
 }
 // ---- a batch in pieces, each on a stream of its own ---------------------------------------------------------------------
@@ -1246,14 +1172,7 @@ int piece_enqueue(kmp_batch_ctx* c, u32 p, u32 pieces, const void* d_src, const 
     m.tables = c->tables; for (int ts_ = 0; ts_ < 4; ts_++) m.tseg[ts_] = c->tseg[ts_]; m.tseg_n = c->tseg_n; m.team_epoch = c->team_epoch;
     m.counter = c->counter + p; m.flags = c->knob.match_flags; m.block_base = p * blocks_per_piece;
     u32 blocks = (m_n + tpw - 1) / tpw; if (blocks > blocks_per_piece) blocks = blocks_per_piece;
-    switch (c->G) {
-    case 2:  hipLaunchKernelGGL(k_zstd_match<2>, dim3(blocks), dim3(64), 0, st, m); break;
-    case 4:  hipLaunchKernelGGL(k_zstd_match<4>, dim3(blocks), dim3(64), 0, st, m); break;
-    case 8:  hipLaunchKernelGGL(k_zstd_match<8>, dim3(blocks), dim3(64), 0, st, m); break;
-    case 16: hipLaunchKernelGGL(k_zstd_match<16>, dim3(blocks), dim3(64), 0, st, m); break;
-    case 32: hipLaunchKernelGGL(k_zstd_match<32>, dim3(blocks), dim3(64), 0, st, m); break;
-    default: hipLaunchKernelGGL(k_zstd_match<64>, dim3(blocks), dim3(64), 0, st, m); break;
-    }
+    by_team_width(c->G, [&](auto w) { hipLaunchKernelGGL(k_zstd_match<decltype(w)::value>, dim3(blocks), dim3(64), 0, st, m); });
     HIP_TRY(hipGetLastError());
     KEntropyArgs e;
     e.src = (const u8*)d_src; e.in_off = d_in_off + first; e.in_len = c->len_ok + first; e.n_slices = m_n;
@@ -1267,7 +1186,6 @@ int piece_enqueue(kmp_batch_ctx* c, u32 p, u32 pieces, const void* d_src, const 
     HIP_TRY(hipEventRecord(c->ev_piece[p], st));
     return KMP_OK;
 }
-void pieces_end(kmp_batch_ctx* c, u32 pieces) { c->have_done = 0; c->pieces_pending = pieces; c->last_chunks = pieces; }
 
 extern "C" int kmp_zstd_compress_batch_pieces(kmp_batch_ctx* c, const void* d_src, const uint64_t* d_in_off, const uint32_t* d_in_len, uint32_t n,
                                               void* d_dst, const uint64_t* d_out_off, uint32_t* d_out_len, uint32_t pieces, void* const* hip_streams)
@@ -1276,8 +1194,8 @@ extern "C" int kmp_zstd_compress_batch_pieces(kmp_batch_ctx* c, const void* d_sr
     if (n > c->max_slices) { g_last_error = "kmp_zstd_compress_batch_pieces: n exceeds the context's max_slices"; return KMP_ERR_CAPACITY; }
     KMP_TRY(pieces_begin(c, pieces, hip_streams));
     if (n == 0) return KMP_OK;
-    for (u32 p = 0; p < pieces; p++) KMP_TRY(piece_enqueue(c, p, pieces, d_src, d_in_off, d_in_len, n, d_dst, d_out_off, d_out_len, (hipStream_t)hip_streams[p]));
-    pieces_end(c, pieces);
+    pieces_end end = { c, pieces, hip_streams, 0 };
+    for (; end.queued < pieces; end.queued++) KMP_TRY(piece_enqueue(c, end.queued, pieces, d_src, d_in_off, d_in_len, n, d_dst, d_out_off, d_out_len, (hipStream_t)hip_streams[end.queued]));
     return KMP_OK;
 }
 // frame i of a piece straight into the caller's HOST memory (registered / pinned: h_dst is its device-visible address): what the
@@ -1332,19 +1250,23 @@ void ensure_pre_staging(kmp_batch_ctx* c)
     if (fit >= 1024u) fit &= ~1023ull;                           // (whole workgroups of every kernel)
     u32 const ps = (u32)fit;
     c->pre_blk_cap = blk_cap;
-    if (ps && (c->knob.decode_pre & 1u)) {
-        if (hipMalloc((void**)&c->pre_stage, (size_t)ps * seq_cap * 8u) == hipSuccess &&
-            hipMalloc((void**)&c->pre_blk, (size_t)ps * blk_cap * sizeof(KPreBlk)) == hipSuccess &&
-            hipMalloc((void**)&c->pre_nblk, (size_t)ps * 4u) == hipSuccess &&
-            hipMalloc((void**)&c->pre_sort, ((size_t)ps * 2u + KXP_SORT_BUCKETS) * 4u) == hipSuccess) { c->pre_seq_cap = seq_cap; c->pre_slices = ps; }
-        else { (void)hipGetLastError(); (void)hipFree(c->pre_stage); (void)hipFree(c->pre_blk); (void)hipFree(c->pre_nblk); (void)hipFree(c->pre_sort); c->pre_stage = nullptr; c->pre_blk = nullptr; c->pre_nblk = nullptr; c->pre_sort = nullptr; }
-    }
-    if (ps && (c->knob.decode_pre & 2u)) {
-        if (hipMalloc((void**)&c->pre_lits, (size_t)ps * lit_cap) == hipSuccess &&
-            hipMalloc((void**)&c->pre_lit, (size_t)ps * blk_cap * sizeof(KPreLit)) == hipSuccess &&
-            hipMalloc((void**)&c->pre_nlit, (size_t)ps * 4u) == hipSuccess) { c->pre_lit_cap = lit_cap; c->pre_slices = ps; }
-        else { (void)hipGetLastError(); (void)hipFree(c->pre_lits); (void)hipFree(c->pre_lit); (void)hipFree(c->pre_nlit); c->pre_lits = nullptr; c->pre_lit = nullptr; c->pre_nlit = nullptr; }
-    }
+    auto seqs = [&](pre_seq_part& q) {
+        KMP_TRY(q.stage.alloc((size_t)ps * seq_cap * 8u));
+        KMP_TRY(q.blk.alloc((size_t)ps * blk_cap * sizeof(KPreBlk)));
+        KMP_TRY(q.nblk.alloc((size_t)ps * 4u));
+        KMP_TRY(q.sort.alloc(((size_t)ps * 2u + KXP_SORT_BUCKETS) * 4u));
+        q.seq_cap = seq_cap;
+        return KMP_OK;
+    };
+    auto lits = [&](pre_lit_part& q) {
+        KMP_TRY(q.lits.alloc((size_t)ps * lit_cap));
+        KMP_TRY(q.rec.alloc((size_t)ps * blk_cap * sizeof(KPreLit)));
+        KMP_TRY(q.nrec.alloc((size_t)ps * 4u));
+        q.lit_cap = lit_cap;
+        return KMP_OK;
+    };
+    if (ps && (c->knob.decode_pre & 1u) && build_part(c->pre_seq, KMP_PART_PRE_SEQ, seqs) == KMP_OK) c->pre_slices = ps;
+    if (ps && (c->knob.decode_pre & 2u) && build_part(c->pre_lit, KMP_PART_PRE_LIT, lits) == KMP_OK) c->pre_slices = ps;
 }
 
 // the counting sort behind the lane-per-entry kernels' slot order (key, rank, permutation: three small launches)
@@ -1395,34 +1317,38 @@ static int zstd_decompress_impl(kmp_batch_ctx* c, const void* d_src, const uint6
         HIP_TRY(hipStreamSynchronize(st));
         HIP_TRY(hipMemcpy(head, d_dict, hn, hipMemcpyDeviceToHost));
         u64 hsh = 1469598103934665603ull; for (u32 i = 0; i < hn; i++) { hsh ^= head[i]; hsh *= 1099511628211ull; }
-        if (c->ddict_ptr != d_dict || c->ddict_size != dict_size || c->ddict_hash != hsh) {
+        if (!c->ddict || c->ddict->ptr != d_dict || c->ddict->size != dict_size || c->ddict->hash != hsh) {
             KDictDPrior dp; size_t off = 0;
             int const formatted = cdict_parse_formatted(head, dict_size, nullptr, &off, &dp, hn);
             if (formatted < 0) { g_last_error = "kmp_zstd_decompress_batch_dict: the dictionary starts with zstd's dictionary magic but its header is damaged (libzstd: Dictionary is corrupted)"; return KMP_ERR_ARG; }
-            (void)hipFree(c->d_dprior); c->d_dprior = nullptr;
-            if (formatted) {
-                HIP_TRY(hipMalloc((void**)&c->d_dprior, sizeof(KDictDPrior)));
-                HIP_TRY(hipMemcpy(c->d_dprior, &dp, sizeof(KDictDPrior), hipMemcpyHostToDevice));
-                c->ddict_off = (u32)off; c->ddict_id = dp.dictID; c->ddict_rep[0] = dp.rep[0]; c->ddict_rep[1] = dp.rep[1]; c->ddict_rep[2] = dp.rep[2];
-            } else { c->ddict_off = 0; c->ddict_id = 0; }
-            c->ddict_ptr = d_dict; c->ddict_size = dict_size; c->ddict_hash = hsh;
+            c->ddict.reset();
+            auto fill = [&](ddict_part& q) {
+                if (formatted) {
+                    KMP_TRY(q.prior.alloc(sizeof(KDictDPrior), "hipMalloc(dictionary entropy tables)"));
+                    HIP_TRY(hipMemcpy(q.prior, &dp, sizeof(KDictDPrior), hipMemcpyHostToDevice));
+                    q.off = (u32)off; q.id = dp.dictID; q.rep[0] = dp.rep[0]; q.rep[1] = dp.rep[1]; q.rep[2] = dp.rep[2];
+                }
+                q.ptr = d_dict; q.size = dict_size; q.hash = hsh;
+                return KMP_OK;
+            };
+            KMP_TRY(build_part(c->ddict, KMP_PART_DDICT, fill));
         }
-        if (c->d_dprior) {
-            d.dict = (const u8*)d_dict + c->ddict_off; d.dict_size = dict_size - c->ddict_off; d.dprior = c->d_dprior; d.dict_id = c->ddict_id;
-            start_rep[0] = c->ddict_rep[0]; start_rep[1] = c->ddict_rep[1]; start_rep[2] = c->ddict_rep[2];
+        ddict_part const& q = *c->ddict;
+        if (q.prior) {
+            d.dict = (const u8*)d_dict + q.off; d.dict_size = dict_size - q.off; d.dprior = q.prior; d.dict_id = q.id;
+            start_rep[0] = q.rep[0]; start_rep[1] = q.rep[1]; start_rep[2] = q.rep[2];
         }
     }
-    // Staging for what the pre-decode kernels leave (8 bytes per sequence -- a frame of S bytes holds at most S / 3 -- and
-    // the literals): allocated on the first call, for as many entries as 48 GiB hold (all of them for the bench's batches;
-    // a larger batch goes through in pieces, one after the other, that reuse the staging).
+    // The pre-decoders' staging (ensure_pre_staging) serves batches of KMP_PRE_MIN_BATCH entries or more.
     // (a small batch -- the one-frame contexts of the streaming entry points above all -- goes straight to k_zstd_decode: a quad
     // or a lane doing a whole frame's serial decode first is the old serial cost plus a second pass, and the staging is memory)
     bool const use_pre = n >= env_pre_min_batch();
     if (use_pre) ensure_pre_staging(c);
+    pre_seq_part const* const ps = use_pre ? c->pre_seq.get() : nullptr; pre_lit_part const* const pl = use_pre ? c->pre_lit.get() : nullptr;
     d.pre_stage = nullptr; d.pre_seq_cap = 0; d.pre_blk = nullptr; d.pre_blk_cap = c->pre_blk_cap; d.pre_nblk = nullptr;
     d.pre_lits = nullptr; d.pre_lit_cap = 0; d.pre_lit = nullptr; d.pre_nlit = nullptr;
-    if (c->profiling) HIP_TRY(hipEventRecord(c->ev[4], st));
-    if (!use_pre || (!c->pre_stage && !c->pre_lits)) {
+    if (c->profiling) HIP_TRY(hipEventRecord(c->decode_t.start, st));
+    if (!ps && !pl) {
         hipLaunchKernelGGL(k_zstd_decode, dim3(n), dim3(64), c->knob.decode_pad, st, d);   // padding = occupancy experiment only
         HIP_TRY(hipGetLastError());
     } else {
@@ -1433,43 +1359,43 @@ static int zstd_decompress_impl(kmp_batch_ctx* c, const void* d_src, const uint6
         if (c->knob.decode_pieces > pieces && n >= 8192u) pieces = c->knob.decode_pieces;
         u32 per = ((n + pieces - 1) / pieces + 63u) & ~63u;
         if (per > c->pre_slices) per = c->pre_slices;
-        u32* const sort_key = c->pre_sort; u32* const sort_perm = c->pre_sort ? c->pre_sort + c->pre_slices : nullptr; u32* const sort_hist = c->pre_sort ? c->pre_sort + 2u * (size_t)c->pre_slices : nullptr;
+        u32* const sort_key = ps ? ps->sort.p : nullptr; u32* const sort_perm = ps ? ps->sort + c->pre_slices : nullptr; u32* const sort_hist = ps ? ps->sort + 2u * (size_t)c->pre_slices : nullptr;
         for (u32 first = 0; first < n; first += per) {
             u32 const m = (n - first < per) ? n - first : per;
-            bool const sorted = c->pre_stage && c->knob.decode_sort != 0 && m >= 1024u;
+            bool const sorted = ps && c->knob.decode_sort != 0 && m >= 1024u;
             if (sorted) KMP_TRY(size_sort(c, st, d.src, d_in_off + first, d_in_len + first, m, sort_key, sort_hist, sort_perm, 0));
             KDecodeArgs q = d;
             q.in_off = d_in_off + first; q.in_len = d_in_len + first; q.n_slices = m;
             q.out_off = d_out_off + first; q.out_cap = d_out_cap + first; q.out_len = d_out_len + first; q.status = d_status + first;
             q.lits = c->lits + (size_t)first * c->lit_cap;
-            if (c->pre_stage) {
+            if (ps) {
                 // (st2 starts where st stands: behind the previous piece's k_zstd_decode, which read the staging)
                 HIP_TRY(hipEventRecord(c->ev_pre[0], st)); HIP_TRY(hipStreamWaitEvent(c->st2, c->ev_pre[0], 0));
                 KPreArgs p;
                 p.perm = sorted ? sort_perm : nullptr;
                 p.src = d.src; p.in_off = q.in_off; p.in_len = q.in_len; p.n_slices = m;
-                p.stage = c->pre_stage; p.seq_cap = c->pre_seq_cap; p.blk = c->pre_blk; p.blk_cap = c->pre_blk_cap; p.nblk = c->pre_nblk;
+                p.stage = ps->stage; p.seq_cap = ps->seq_cap; p.blk = ps->blk; p.blk_cap = c->pre_blk_cap; p.nblk = ps->nblk;
                 p.rep[0] = start_rep[0]; p.rep[1] = start_rep[1]; p.rep[2] = start_rep[2];
                 hipLaunchKernelGGL(k_zstd_seq_predecode, dim3((m + KXP_FRAMES - 1) / KXP_FRAMES), dim3(4 * KXP_FRAMES), 0, c->st2, p);
                 HIP_TRY(hipGetLastError());
                 HIP_TRY(hipEventRecord(c->ev_pre[1], c->st2));
-                q.pre_stage = c->pre_stage; q.pre_seq_cap = c->pre_seq_cap; q.pre_blk = c->pre_blk; q.pre_nblk = c->pre_nblk;
+                q.pre_stage = ps->stage; q.pre_seq_cap = ps->seq_cap; q.pre_blk = ps->blk; q.pre_nblk = ps->nblk;
             }
-            if (c->pre_lits) {
+            if (pl) {
                 KLitArgs p;
                 p.perm = sorted ? sort_perm : nullptr;
                 p.src = d.src; p.in_off = q.in_off; p.in_len = q.in_len; p.n_slices = m;
-                p.lits = c->pre_lits; p.lit_cap = c->pre_lit_cap; p.rec = c->pre_lit; p.blk_cap = c->pre_blk_cap; p.nrec = c->pre_nlit;
+                p.lits = pl->lits; p.lit_cap = pl->lit_cap; p.rec = pl->rec; p.blk_cap = c->pre_blk_cap; p.nrec = pl->nrec;
                 hipLaunchKernelGGL(k_zstd_lit_predecode, dim3((m + KXL_FRAMES - 1) / KXL_FRAMES), dim3(64), 0, st, p);
                 HIP_TRY(hipGetLastError());
-                q.pre_lits = c->pre_lits; q.pre_lit_cap = c->pre_lit_cap; q.pre_lit = c->pre_lit; q.pre_nlit = c->pre_nlit;
+                q.pre_lits = pl->lits; q.pre_lit_cap = pl->lit_cap; q.pre_lit = pl->rec; q.pre_nlit = pl->nrec;
             }
-            if (c->pre_stage) HIP_TRY(hipStreamWaitEvent(st, c->ev_pre[1], 0));
+            if (ps) HIP_TRY(hipStreamWaitEvent(st, c->ev_pre[1], 0));
             hipLaunchKernelGGL(k_zstd_decode, dim3(m), dim3(64), c->knob.decode_pad, st, q);
             HIP_TRY(hipGetLastError());
         }
     }
-    if (c->profiling) { HIP_TRY(hipEventRecord(c->ev[5], st)); c->ev_valid[2] = 1; }
+    if (c->profiling) { HIP_TRY(hipEventRecord(c->decode_t.end, st)); c->decode_timed = 1; }
     return batch_end(c, st, nullptr, n, 0, nullptr, nullptr);
 }
 

@@ -63,25 +63,15 @@ template <class F> static void host_parallel(u32 threads, u32 count, F const& fn
 struct host_job { const u8* in; u32 len; u8* out; u32 out_cap; u32 out_len; u32 status; std::vector<u8>* out_vec; bool done; int batch_rc; };
 
 struct host_engine {
-    int device; kmp_batch_ctx* batch; u32 cap_slices; u32 slice_cap; size_t stride;
-    u8 *h_in, *h_out; u64 *h_off, *h_doff; u32 *h_len, *h_cap, *h_st;             // pinned
-    u8 *d_in, *d_out, *d_dense; u64 *d_off, *d_ooff, *d_doff; u32 *d_len, *d_olen, *d_cap, *d_st;
-    size_t in_bytes, out_bytes;
-    hipStream_t st;
+    int device = 0; u32 cap_slices = 0; u32 slice_cap = 0; size_t stride = 0;
+    pinned_buf<u8> h_in, h_out; pinned_buf<u64> h_off, h_doff; pinned_buf<u32> h_len, h_cap, h_st;
+    dev_buf<u8> d_in, d_out, d_dense; dev_buf<u64> d_off, d_ooff, d_doff; dev_buf<u32> d_len, d_olen, d_cap, d_st;
+    size_t in_bytes = 0, out_bytes = 0;
+    hip_stream st;
+    batch_ptr batch;
     std::mutex run_mutex;                                                            // one run at a time (the staging is shared)
+    ~host_engine() { (void)hipSetDevice(device); }                                   // (what it holds is freed on its device)
 };
-
-static void host_engine_free(host_engine* e)
-{
-    if (!e) return;
-    (void)hipSetDevice(e->device);
-    if (e->batch) kmp_batch_destroy(e->batch);
-    (void)hipHostFree(e->h_in); (void)hipHostFree(e->h_out); (void)hipHostFree(e->h_off); (void)hipHostFree(e->h_doff); (void)hipHostFree(e->h_len); (void)hipHostFree(e->h_cap); (void)hipHostFree(e->h_st);
-    (void)hipFree(e->d_in); (void)hipFree(e->d_out); (void)hipFree(e->d_dense); (void)hipFree(e->d_off); (void)hipFree(e->d_ooff); (void)hipFree(e->d_doff);
-    (void)hipFree(e->d_len); (void)hipFree(e->d_olen); (void)hipFree(e->d_cap); (void)hipFree(e->d_st);
-    if (e->st) (void)hipStreamDestroy(e->st);
-    delete e;
-}
 
 // Engines per device and process, made on first use.  Slot 0: batches of up to KMP_HOST_BATCH_SLICES (default 1024) slices of up to
 // 128 KiB -- the coalescer's and the small calls'.  Slots 1 ..: the bulk engines of large DECODE batches (KMP_HOST_BULK_SLICES,
@@ -102,38 +92,37 @@ static host_engine* host_engine_get(int device, int slot = 0)
     if (T.engines[device][slot]) return T.engines[device][slot];
     if (T.failed[device][slot] && std::chrono::steady_clock::now() - T.failed_at[device][slot] < std::chrono::seconds(5)) { g_last_error = "host batch engine: allocation failed a moment ago"; return nullptr; }
     device_guard const on(device);
-    host_engine* e = new (std::nothrow) host_engine();
+    std::unique_ptr<host_engine> e(new (std::nothrow) host_engine());
     if (!e) return nullptr;
-    e->device = device; e->batch = nullptr; e->st = nullptr;
-    e->h_in = e->h_out = nullptr; e->h_off = e->h_doff = nullptr; e->h_len = e->h_cap = e->h_st = nullptr;
-    e->d_in = e->d_out = e->d_dense = nullptr; e->d_off = e->d_ooff = e->d_doff = nullptr; e->d_len = e->d_olen = e->d_cap = e->d_st = nullptr;
+    e->device = device;
     e->cap_slices = slot == 0 ? env_u32("KMP_HOST_BATCH_SLICES", 1024) : env_u32("KMP_HOST_BULK_SLICES", 8192);
     if (e->cap_slices < 16) e->cap_slices = 16; if (e->cap_slices > 65536) e->cap_slices = 65536;
     e->slice_cap = KMP_MAX_SLICE_BYTES;
     e->stride = (kmp_zstd_compress_bound(e->slice_cap) + 8 + 63) & ~(size_t)63;
     size_t const n = e->cap_slices;
     e->in_bytes = n * ((size_t)e->slice_cap + 64); e->out_bytes = n * e->stride;
-    bool ok = batch_create_packed(&e->batch, device, e->cap_slices, e->slice_cap) == KMP_OK;       // (its arena packed: an engine is not the place to spend a span on)
-    ok = ok && hipStreamCreateWithFlags(&e->st, hipStreamNonBlocking) == hipSuccess;
-    ok = ok && hipHostMalloc((void**)&e->h_in, e->in_bytes) == hipSuccess && hipHostMalloc((void**)&e->h_out, e->out_bytes) == hipSuccess;
-    ok = ok && hipHostMalloc((void**)&e->h_off, (n + 1) * 8) == hipSuccess && hipHostMalloc((void**)&e->h_doff, (n + 1) * 8) == hipSuccess;
-    ok = ok && hipHostMalloc((void**)&e->h_len, n * 4) == hipSuccess && hipHostMalloc((void**)&e->h_cap, n * 4) == hipSuccess && hipHostMalloc((void**)&e->h_st, n * 4) == hipSuccess;
-    ok = ok && hipMalloc((void**)&e->d_in, e->in_bytes) == hipSuccess && hipMalloc((void**)&e->d_out, e->out_bytes + 64) == hipSuccess && hipMalloc((void**)&e->d_dense, e->out_bytes + 64) == hipSuccess;
-    ok = ok && hipMalloc((void**)&e->d_off, (n + 1) * 8) == hipSuccess && hipMalloc((void**)&e->d_ooff, (n + 1) * 8) == hipSuccess && hipMalloc((void**)&e->d_doff, (n + 1) * 8) == hipSuccess;
-    ok = ok && hipMalloc((void**)&e->d_len, n * 4) == hipSuccess && hipMalloc((void**)&e->d_olen, n * 4) == hipSuccess && hipMalloc((void**)&e->d_cap, n * 4) == hipSuccess && hipMalloc((void**)&e->d_st, n * 4) == hipSuccess;
+    kmp_batch_ctx* bc = nullptr;
+    bool ok = batch_create_packed(&bc, device, e->cap_slices, e->slice_cap) == KMP_OK;       // (its arena packed: an engine is not the place to spend a span on)
+    e->batch.reset(bc);
+    ok = ok && e->st.create(hipStreamNonBlocking) == KMP_OK;
+    ok = ok && e->h_in.alloc(e->in_bytes) == KMP_OK && e->h_out.alloc(e->out_bytes) == KMP_OK;
+    ok = ok && e->h_off.alloc((n + 1) * 8) == KMP_OK && e->h_doff.alloc((n + 1) * 8) == KMP_OK;
+    ok = ok && e->h_len.alloc(n * 4) == KMP_OK && e->h_cap.alloc(n * 4) == KMP_OK && e->h_st.alloc(n * 4) == KMP_OK;
+    ok = ok && e->d_in.alloc(e->in_bytes) == KMP_OK && e->d_out.alloc(e->out_bytes + 64) == KMP_OK && e->d_dense.alloc(e->out_bytes + 64) == KMP_OK;
+    ok = ok && e->d_off.alloc((n + 1) * 8) == KMP_OK && e->d_ooff.alloc((n + 1) * 8) == KMP_OK && e->d_doff.alloc((n + 1) * 8) == KMP_OK;
+    ok = ok && e->d_len.alloc(n * 4) == KMP_OK && e->d_olen.alloc(n * 4) == KMP_OK && e->d_cap.alloc(n * 4) == KMP_OK && e->d_st.alloc(n * 4) == KMP_OK;
     if (ok) {
         // the strided output offsets never change
         for (size_t i = 0; i <= n; i++) e->h_doff[i] = i * e->stride;
         ok = hipMemcpy(e->d_ooff, e->h_doff, (n + 1) * 8, hipMemcpyHostToDevice) == hipSuccess;
     }
     if (!ok) {
-        (void)hipGetLastError(); host_engine_free(e); g_last_error = "host batch engine: allocation failed";
+        (void)hipGetLastError(); e.reset(); g_last_error = "host batch engine: allocation failed";
         T.failed[device][slot] = true; T.failed_at[device][slot] = std::chrono::steady_clock::now();
         return nullptr;
     }
     T.failed[device][slot] = false;
-    T.engines[device][slot] = e;
-    return e;
+    return T.engines[device][slot] = e.release();
 }
 
 // Compresses jobs[0 .. n) (n <= cap_slices, every len <= 128 KiB) at any level the batch call serves: one H2D copy, the device
@@ -154,8 +143,8 @@ static int host_engine_compress(host_engine* e, host_job* jobs, u32 n, int level
     if (pos) HIP_TRY(hipMemcpyAsync(e->d_in, e->h_in, pos, hipMemcpyHostToDevice, e->st));
     HIP_TRY(hipMemcpyAsync(e->d_off, e->h_off, (size_t)n * 8, hipMemcpyHostToDevice, e->st));
     HIP_TRY(hipMemcpyAsync(e->d_len, e->h_len, (size_t)n * 4, hipMemcpyHostToDevice, e->st));
-    KMP_TRY(kmp_zstd_compress_batch_level(e->batch, e->d_in, e->d_off, e->d_len, n, e->d_out, e->d_ooff, e->d_olen, level, e->st));
-    KMP_TRY(kmp_compact_batch(e->batch, e->d_out, e->d_ooff, e->d_olen, n, e->d_dense, e->d_doff, e->st));
+    KMP_TRY(kmp_zstd_compress_batch_level(e->batch.get(), e->d_in, e->d_off, e->d_len, n, e->d_out, e->d_ooff, e->d_olen, level, e->st));
+    KMP_TRY(kmp_compact_batch(e->batch.get(), e->d_out, e->d_ooff, e->d_olen, n, e->d_dense, e->d_doff, e->st));
     HIP_TRY(hipMemcpyAsync(e->h_off, e->d_doff, ((size_t)n + 1) * 8, hipMemcpyDeviceToHost, e->st));
     HIP_TRY(hipStreamSynchronize(e->st));
     size_t const total = (size_t)e->h_off[n];
@@ -164,7 +153,7 @@ static int host_engine_compress(host_engine* e, host_job* jobs, u32 n, int level
     HIP_TRY(hipStreamSynchronize(e->st));
     if (ran) *ran = true;                                                // from here on every job gets its own outcome
     u32 bits = 0;
-    (void)kmp_batch_status(e->batch, &bits, e->st);                       // (the bits of refused slices: cleared here, reported per slice below)
+    (void)kmp_batch_status(e->batch.get(), &bits, e->st);                       // (the bits of refused slices: cleared here, reported per slice below)
     int rc = KMP_OK;
     for (u32 i = 0; i < n; i++) {
         size_t const a = (size_t)e->h_off[i], b = (size_t)e->h_off[i + 1];
@@ -207,7 +196,7 @@ static int host_engine_decompress(host_engine* e, host_job* jobs, u32 n)
     HIP_TRY(hipMemcpyAsync(e->d_len, e->h_len, (size_t)n * 4, hipMemcpyHostToDevice, e->st));
     HIP_TRY(hipMemcpyAsync(e->d_doff, e->h_doff, (size_t)n * 8, hipMemcpyHostToDevice, e->st));
     HIP_TRY(hipMemcpyAsync(e->d_cap, e->h_cap, (size_t)n * 4, hipMemcpyHostToDevice, e->st));
-    KMP_TRY(kmp_zstd_decompress_batch(e->batch, e->d_in, e->d_off, e->d_len, n, e->d_dense, e->d_doff, e->d_cap, e->d_olen, e->d_st, e->st));
+    KMP_TRY(kmp_zstd_decompress_batch(e->batch.get(), e->d_in, e->d_off, e->d_len, n, e->d_dense, e->d_doff, e->d_cap, e->d_olen, e->d_st, e->st));
     HIP_TRY(hipMemcpyAsync(e->h_len, e->d_olen, (size_t)n * 4, hipMemcpyDeviceToHost, e->st));
     HIP_TRY(hipMemcpyAsync(e->h_st, e->d_st, (size_t)n * 4, hipMemcpyDeviceToHost, e->st));
     if (opos) HIP_TRY(hipMemcpyAsync(e->h_out, e->d_dense, opos, hipMemcpyDeviceToHost, e->st));
@@ -260,32 +249,16 @@ static u8* host_range_device_ptr(const void* p, size_t bytes)
 //            on the piece's stream, copy out on s_out, and the worker threads hand the frames out.
 // 65 536 x 64 KiB: 11.4 GB/s through the staged engines of round 3; pinned in and out, pipelined: see bench.py's host_batch_bulk.
 struct bulk_pipe {
-    int device; kmp_batch_ctx* batch; u32 cap_slices, slice_cap, pieces; size_t stride, in_bytes, out_bytes;
-    hipStream_t s_in, s_out, s_piece[KMP_MAX_PIECES];
-    hipEvent_t arrived[KMP_MAX_PIECES], packed[KMP_MAX_PIECES], copied[KMP_MAX_PIECES];
-    u8 *d_in, *d_out, *d_dense; u64 *d_off, *d_ooff, *d_doff, *d_hoff; u32 *d_len, *d_olen, *d_cap, *d_st;
-    u8 *h_in, *h_out;                                         // pinned staging, made when a call first needs it
-    u64 *h_off, *h_doff, *h_tot; u32 *h_len, *h_st;           // pinned
+    int device = 0; u32 cap_slices = 0, slice_cap = 0, pieces = 0; size_t stride = 0, in_bytes = 0, out_bytes = 0;
+    hip_stream s_in, s_out, s_piece[KMP_MAX_PIECES];
+    hip_event arrived[KMP_MAX_PIECES], packed[KMP_MAX_PIECES], copied[KMP_MAX_PIECES];
+    dev_buf<u8> d_in, d_out, d_dense; dev_buf<u64> d_off, d_ooff, d_doff, d_hoff; dev_buf<u32> d_len, d_olen, d_cap, d_st;
+    pinned_buf<u8> h_in, h_out;                               // pinned staging, made when a call first needs it
+    pinned_buf<u64> h_off, h_doff, h_tot; pinned_buf<u32> h_len, h_st;
+    batch_ptr batch;
     std::mutex run_mutex;
+    ~bulk_pipe() { (void)hipSetDevice(device); }              // (what it holds is freed on its device)
 };
-static void bulk_pipe_free(bulk_pipe* b)
-{
-    if (!b) return;
-    (void)hipSetDevice(b->device);
-    if (b->batch) kmp_batch_destroy(b->batch);
-    (void)hipFree(b->d_in); (void)hipFree(b->d_out); (void)hipFree(b->d_dense); (void)hipFree(b->d_off); (void)hipFree(b->d_ooff); (void)hipFree(b->d_doff); (void)hipFree(b->d_hoff);
-    (void)hipFree(b->d_len); (void)hipFree(b->d_olen); (void)hipFree(b->d_cap); (void)hipFree(b->d_st);
-    (void)hipHostFree(b->h_in); (void)hipHostFree(b->h_out); (void)hipHostFree(b->h_off); (void)hipHostFree(b->h_doff); (void)hipHostFree(b->h_tot); (void)hipHostFree(b->h_len); (void)hipHostFree(b->h_st);
-    if (b->s_in) (void)hipStreamDestroy(b->s_in);
-    if (b->s_out) (void)hipStreamDestroy(b->s_out);
-    for (int i = 0; i < KMP_MAX_PIECES; i++) {
-        if (b->s_piece[i]) (void)hipStreamDestroy(b->s_piece[i]);
-        if (b->arrived[i]) (void)hipEventDestroy(b->arrived[i]);
-        if (b->packed[i]) (void)hipEventDestroy(b->packed[i]);
-        if (b->copied[i]) (void)hipEventDestroy(b->copied[i]);
-    }
-    delete b;
-}
 struct bulk_table { std::mutex m; bulk_pipe* pipe[KMP_HOST_DEVICES]; std::mutex call[KMP_HOST_DEVICES]; };      // call[d]: one bulk call per device at a time (it may rebuild the pipe)
 static bulk_table& bulk_tab() { static bulk_table t = {}; return t; }
 // the pipe of `device`, large enough for n slices of up to max_len bytes (rebuilt when it is not)
@@ -300,10 +273,11 @@ static bulk_pipe* bulk_pipe_get(int device, u32 n, u32 max_len)
     bulk_pipe* b = T.pipe[device];
     if (b && b->cap_slices >= want_n && b->slice_cap >= want_len) return b;
     if (b) { std::lock_guard<std::mutex> r(b->run_mutex); }                            // (nobody is inside it: calls hold run_mutex while they run)
-    bulk_pipe_free(b); T.pipe[device] = nullptr;
+    delete b; T.pipe[device] = nullptr;
     device_guard const on(device);
-    b = new (std::nothrow) bulk_pipe();          // (value-initialised: every pointer null)
-    if (!b) return nullptr;
+    std::unique_ptr<bulk_pipe> p(new (std::nothrow) bulk_pipe());
+    if (!p) return nullptr;
+    b = p.get();
     b->device = device; b->cap_slices = want_n; b->slice_cap = want_len; b->pieces = KMP_MAX_PIECES;
     b->stride = (kmp_zstd_compress_bound(want_len) + 8 + 63) & ~(size_t)63;
     size_t const ns = want_n;
@@ -315,24 +289,25 @@ static bulk_pipe* bulk_pipe_get(int device, u32 n, u32 max_len)
         size_t fr = 0, tot = 0; if (hipMemGetInfo(&fr, &tot) != hipSuccess) { (void)hipGetLastError(); fr = 0; }
         int span = (int)((fr / 4) >> 30); if (span > (int)env_u32("KMP_TABLE_SPAN_GIB", 100)) span = (int)env_u32("KMP_TABLE_SPAN_GIB", 100); if (span < 72) span = 0;
         kmp_batch_options o; o.struct_bytes = sizeof o; o.team_lanes = 0; o.table_span_gib = span; o.table_retry = 0;
-        ok = kmp_batch_create_ex(&b->batch, device, want_n, want_len, &o) == KMP_OK;
+        kmp_batch_ctx* bc = nullptr;
+        ok = kmp_batch_create_ex(&bc, device, want_n, want_len, &o) == KMP_OK;
+        b->batch.reset(bc);
     }
-    ok = ok && hipStreamCreateWithFlags(&b->s_in, hipStreamNonBlocking) == hipSuccess && hipStreamCreateWithFlags(&b->s_out, hipStreamNonBlocking) == hipSuccess;
+    ok = ok && b->s_in.create(hipStreamNonBlocking) == KMP_OK && b->s_out.create(hipStreamNonBlocking) == KMP_OK;
     for (int i = 0; ok && i < KMP_MAX_PIECES; i++)
-        ok = hipStreamCreateWithFlags(&b->s_piece[i], hipStreamNonBlocking) == hipSuccess && hipEventCreateWithFlags(&b->arrived[i], hipEventDisableTiming) == hipSuccess &&
-             hipEventCreateWithFlags(&b->packed[i], hipEventDisableTiming) == hipSuccess && hipEventCreateWithFlags(&b->copied[i], hipEventDisableTiming) == hipSuccess;
-    ok = ok && hipMalloc((void**)&b->d_in, b->in_bytes) == hipSuccess && hipMalloc((void**)&b->d_out, b->out_bytes + 64) == hipSuccess && hipMalloc((void**)&b->d_dense, b->out_bytes + 64) == hipSuccess;
-    ok = ok && hipMalloc((void**)&b->d_off, (ns + 1) * 8) == hipSuccess && hipMalloc((void**)&b->d_ooff, (ns + 1) * 8) == hipSuccess && hipMalloc((void**)&b->d_doff, (ns + KMP_MAX_PIECES) * 8) == hipSuccess && hipMalloc((void**)&b->d_hoff, (ns + 1) * 8) == hipSuccess;
-    ok = ok && hipMalloc((void**)&b->d_len, ns * 4) == hipSuccess && hipMalloc((void**)&b->d_olen, ns * 4) == hipSuccess && hipMalloc((void**)&b->d_cap, ns * 4) == hipSuccess && hipMalloc((void**)&b->d_st, ns * 4) == hipSuccess;
-    ok = ok && hipHostMalloc((void**)&b->h_off, (ns + 1) * 8) == hipSuccess && hipHostMalloc((void**)&b->h_doff, (ns + KMP_MAX_PIECES) * 8) == hipSuccess && hipHostMalloc((void**)&b->h_tot, 64 * 8) == hipSuccess;
-    ok = ok && hipHostMalloc((void**)&b->h_len, ns * 4) == hipSuccess && hipHostMalloc((void**)&b->h_st, ns * 4) == hipSuccess;
+        ok = b->s_piece[i].create(hipStreamNonBlocking) == KMP_OK && b->arrived[i].create(hipEventDisableTiming) == KMP_OK &&
+             b->packed[i].create(hipEventDisableTiming) == KMP_OK && b->copied[i].create(hipEventDisableTiming) == KMP_OK;
+    ok = ok && b->d_in.alloc(b->in_bytes) == KMP_OK && b->d_out.alloc(b->out_bytes + 64) == KMP_OK && b->d_dense.alloc(b->out_bytes + 64) == KMP_OK;
+    ok = ok && b->d_off.alloc((ns + 1) * 8) == KMP_OK && b->d_ooff.alloc((ns + 1) * 8) == KMP_OK && b->d_doff.alloc((ns + KMP_MAX_PIECES) * 8) == KMP_OK && b->d_hoff.alloc((ns + 1) * 8) == KMP_OK;
+    ok = ok && b->d_len.alloc(ns * 4) == KMP_OK && b->d_olen.alloc(ns * 4) == KMP_OK && b->d_cap.alloc(ns * 4) == KMP_OK && b->d_st.alloc(ns * 4) == KMP_OK;
+    ok = ok && b->h_off.alloc((ns + 1) * 8) == KMP_OK && b->h_doff.alloc((ns + KMP_MAX_PIECES) * 8) == KMP_OK && b->h_tot.alloc(64 * 8) == KMP_OK;
+    ok = ok && b->h_len.alloc(ns * 4) == KMP_OK && b->h_st.alloc(ns * 4) == KMP_OK;
     if (ok) {
         for (size_t i = 0; i <= ns; i++) b->h_off[i] = i * b->stride;
         ok = hipMemcpy(b->d_ooff, b->h_off, (ns + 1) * 8, hipMemcpyHostToDevice) == hipSuccess;
     }
-    if (!ok) { (void)hipGetLastError(); bulk_pipe_free(b); g_last_error = "host batch: the bulk compressor could not be made (memory)"; return nullptr; }
-    T.pipe[device] = b;
-    return b;
+    if (!ok) { (void)hipGetLastError(); g_last_error = "host batch: the bulk compressor could not be made (memory)"; return nullptr; }
+    return T.pipe[device] = p.release();
 }
 
 // one pass: n <= cap_slices slices.  src_dev / dst_dev: device-visible addresses of the caller's whole source / destination ranges
@@ -374,8 +349,8 @@ static int bulk_pipe_run(bulk_pipe* b, int level, const u8* h_src, const u8* src
     }
     base[P] = pos;
     if (pos > b->in_bytes) { g_last_error = "host batch: the batch exceeds the bulk compressor's staging"; return KMP_ERR_CAPACITY; }
-    if (need_stage_in && !b->h_in && hipHostMalloc((void**)&b->h_in, b->in_bytes) != hipSuccess) { (void)hipGetLastError(); b->h_in = nullptr; g_last_error = "host batch: no pinned memory for the input staging"; return KMP_ERR_HIP; }
-    if (!dst_dev && !b->h_out && hipHostMalloc((void**)&b->h_out, b->out_bytes) != hipSuccess) { (void)hipGetLastError(); b->h_out = nullptr; g_last_error = "host batch: no pinned memory for the output staging"; return KMP_ERR_HIP; }
+    if (need_stage_in && !b->h_in && b->h_in.alloc(b->in_bytes, "host batch: no pinned memory for the input staging") != KMP_OK) return KMP_ERR_HIP;
+    if (!dst_dev && !b->h_out && b->h_out.alloc(b->out_bytes, "host batch: no pinned memory for the output staging") != KMP_OK) return KMP_ERR_HIP;
     // the small tables first (the kernels of every piece read them)
     HIP_TRY(hipMemcpyAsync(b->d_off, b->h_off, (size_t)n * 8, hipMemcpyHostToDevice, b->s_in));
     HIP_TRY(hipMemcpyAsync(b->d_len, b->h_len, (size_t)n * 4, hipMemcpyHostToDevice, b->s_in));
@@ -384,8 +359,9 @@ static int bulk_pipe_run(bulk_pipe* b, int level, const u8* h_src, const u8* src
         HIP_TRY(hipMemcpyAsync(b->d_cap, out_cap, (size_t)n * 4, hipMemcpyHostToDevice, b->s_in));
     }
     void* streams[KMP_MAX_PIECES]; for (u32 p = 0; p < P; p++) streams[p] = b->s_piece[p];
-    KMP_TRY(pieces_begin(b->batch, P, streams));
-    for (u32 p = 0; p < P; p++) {
+    KMP_TRY(pieces_begin(b->batch.get(), P, streams));
+    for (pieces_end end = { b->batch.get(), P, streams, 0 }; end.queued < P; ) {         // (`end` closes the batch in pieces when the loop is left, whichever way)
+        u32 const p = end.queued;
         u32 first = 0, cnt = 0; kmp_batch_piece_range(n, P, p, &first, &cnt);
         if (cnt && span[p]) {
             if (direct_in[p]) HIP_TRY(hipMemcpyAsync(b->d_in + base[p], src_dev + in_off[first], span[p], hipMemcpyHostToDevice, b->s_in));
@@ -396,17 +372,17 @@ static int bulk_pipe_run(bulk_pipe* b, int level, const u8* h_src, const u8* src
         }
         HIP_TRY(hipEventRecord(b->arrived[p], b->s_in));
         HIP_TRY(hipStreamWaitEvent(b->s_piece[p], b->arrived[p], 0));
-        if (level == 3) KMP_TRY(piece_enqueue(b->batch, p, P, b->d_in, b->d_off, b->d_len, n, b->d_out, b->d_ooff, b->d_olen, b->s_piece[p]));
+        if (level == 3) KMP_TRY(piece_enqueue(b->batch.get(), p, P, b->d_in, b->d_off, b->d_len, n, b->d_out, b->d_ooff, b->d_olen, b->s_piece[p]));
+        end.queued++;
         if (!cnt) { HIP_TRY(hipEventRecord(b->packed[p], b->s_piece[p])); continue; }
-        if (dst_dev) KMP_TRY(scatter_frames(b->batch, b->s_piece[p], b->d_out, b->d_ooff + first, b->d_olen + first, cnt, dst_dev, b->d_hoff + first, b->d_cap + first, b->d_st + first));
+        if (dst_dev) KMP_TRY(scatter_frames(b->batch.get(), b->s_piece[p], b->d_out, b->d_ooff + first, b->d_olen + first, cnt, dst_dev, b->d_hoff + first, b->d_cap + first, b->d_st + first));
         else {
             // the piece's frames, densely packed, into its own part of d_dense (worst-case placement), the offsets behind those of the pieces before
-            KMP_TRY(kmp_compact_batch(b->batch, b->d_out, b->d_ooff + first, b->d_olen + first, cnt, b->d_dense + (size_t)first * b->stride, b->d_doff + first + p, b->s_piece[p]));
+            KMP_TRY(kmp_compact_batch(b->batch.get(), b->d_out, b->d_ooff + first, b->d_olen + first, cnt, b->d_dense + (size_t)first * b->stride, b->d_doff + first + p, b->s_piece[p]));
             HIP_TRY(hipMemcpyAsync(b->h_doff + first + p, b->d_doff + first + p, ((size_t)cnt + 1) * 8, hipMemcpyDeviceToHost, b->s_piece[p]));
         }
         HIP_TRY(hipEventRecord(b->packed[p], b->s_piece[p]));
     }
-    pieces_end(b->batch, P);
     int rc = KMP_OK;
     if (dst_dev) {
         // everything is queued: the frames land in the caller's memory as the pieces finish
@@ -588,14 +564,14 @@ extern "C" int kmp_host_engines_release(int device)
             std::lock_guard<std::mutex> g(T.m);
             for (int s = 0; s < KMP_HOST_ENGINES; s++) if (T.engines[d][s]) {
                 { std::lock_guard<std::mutex> r(T.engines[d][s]->run_mutex); }
-                host_engine_free(T.engines[d][s]); T.engines[d][s] = nullptr; T.failed[d][s] = false;
+                delete T.engines[d][s]; T.engines[d][s] = nullptr; T.failed[d][s] = false;
             }
         }
         {
             bulk_table& B = bulk_tab();
             std::lock_guard<std::mutex> one_call(B.call[d]);
             std::lock_guard<std::mutex> g(B.m);
-            if (B.pipe[d]) { { std::lock_guard<std::mutex> r(B.pipe[d]->run_mutex); } bulk_pipe_free(B.pipe[d]); B.pipe[d] = nullptr; }
+            if (B.pipe[d]) { { std::lock_guard<std::mutex> r(B.pipe[d]->run_mutex); } delete B.pipe[d]; B.pipe[d] = nullptr; }
         }
     }
     return KMP_OK;

@@ -12,7 +12,10 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <memory>
+#include <new>
 #include <string>
+#include <utility>
 #include "../../include/kompressor_hip.h"
 
 typedef uint8_t  u8;
@@ -21,6 +24,7 @@ typedef uint32_t u32;
 typedef uint64_t u64;
 
 struct KSeq; struct KSliceMeta; struct KFrameState; struct KdBest; struct KdSliceMeta; struct KdBlockInfo; struct KPreBlk; struct KPreLit;
+struct KDictPrior; struct KDictDPrior;
 
 // --------------------------------------------------------------------------
 // errors
@@ -45,58 +49,155 @@ u32 env_u32(const char* name, u32 dflt);
 #endif
 
 // --------------------------------------------------------------------------
+// owners of device resources
+// --------------------------------------------------------------------------
+// Move-only owners, the only code that frees device or pinned memory, events and streams.  A buffer records its byte count and
+// converts to its pointer (the kernels' argument structs take plain views).  alloc / create release what the owner held, then
+// return KMP_OK or KMP_ERR_HIP (the sticky HIP error cleared; g_last_error set unless `what` is null: an allocation allowed to fail).
+template <class T, bool Pinned> struct kmp_buf {
+    T* p = nullptr; size_t bytes = 0;
+    kmp_buf() = default;
+    kmp_buf(kmp_buf&& o) noexcept : p(o.p), bytes(o.bytes) { o.p = nullptr; o.bytes = 0; }
+    kmp_buf& operator=(kmp_buf o) noexcept { std::swap(p, o.p); std::swap(bytes, o.bytes); return *this; }
+    ~kmp_buf() { reset(); }
+    void reset() { if (p) (void)(Pinned ? hipHostFree(p) : hipFree(p)); p = nullptr; bytes = 0; }
+    int alloc(size_t n, const char* what = nullptr)
+    {
+        reset();
+        hipError_t const e = Pinned ? hipHostMalloc((void**)&p, n) : hipMalloc((void**)&p, n);
+        if (e != hipSuccess) { p = nullptr; (void)hipGetLastError(); return what ? hip_fail(e, what) : KMP_ERR_HIP; }
+        bytes = n;
+        return KMP_OK;
+    }
+    operator T*() const { return p; }
+};
+template <class T> using dev_buf = kmp_buf<T, false>;
+template <class T> using pinned_buf = kmp_buf<T, true>;
+template <class H, hipError_t (*Create)(H*, unsigned), hipError_t (*Destroy)(H)> struct kmp_handle {
+    H h = nullptr;
+    kmp_handle() = default;
+    kmp_handle(kmp_handle&& o) noexcept : h(o.h) { o.h = nullptr; }
+    kmp_handle& operator=(kmp_handle o) noexcept { std::swap(h, o.h); return *this; }
+    ~kmp_handle() { if (h) (void)Destroy(h); }
+    int create(unsigned flags)
+    {
+        hipError_t const e = Create(&h, flags);       // (on an empty owner)
+        if (e != hipSuccess) { h = nullptr; (void)hipGetLastError(); return hip_fail(e, "creating a HIP event / stream"); }
+        return KMP_OK;
+    }
+    operator H() const { return h; }
+};
+using hip_event = kmp_handle<hipEvent_t, hipEventCreateWithFlags, hipEventDestroy>;
+using hip_stream = kmp_handle<hipStream_t, hipStreamCreateWithFlags, hipStreamDestroy>;
+
+// The sets a context adds on first use are parts: absent or complete.  build_part makes one locally and moves it into `slot` only
+// when `fill` -- every allocation and clear of the part -- has succeeded; otherwise the slot stays empty and whatever fill
+// allocated is freed.  The ablation build's KMP_TEST_FAIL_PART=<code> fails the named part once fill has succeeded: what a
+// failing last allocation would leave (the earlier ones made, then freed), without a switch in the owners.
+enum { KMP_PART_DEFLATE_LAZY = 1, KMP_PART_DEFLATE_FAST, KMP_PART_LAZY_LEVELS, KMP_PART_DICT, KMP_PART_FLAT_TABLES, KMP_PART_TABLES4,
+       KMP_PART_CHAIN_TABLES4, KMP_PART_DDICT, KMP_PART_PRE_SEQ, KMP_PART_PRE_LIT };
+template <class P, class F> int build_part(std::unique_ptr<P>& slot, u32 code, F const& fill)
+{
+    std::unique_ptr<P> p(new (std::nothrow) P());
+    if (!p) { g_last_error = "out of host memory"; return KMP_ERR_HIP; }
+    KMP_TRY(fill(*p));
+#ifdef KMP_ABLATIONS
+    if (KMP_KNOB("KMP_TEST_FAIL_PART", 0) == code) return hip_fail(hipErrorOutOfMemory, "KMP_TEST_FAIL_PART");
+#else
+    (void)code;
+#endif
+    slot = std::move(p);
+    return KMP_OK;
+}
+template <class P> size_t part_bytes(std::unique_ptr<P> const& p) { return p ? p->bytes() : 0; }
+
+// parser tables (+ team epochs): levels 1 / 2 and the dictionary parser (one piece, when the level-3 tables are spread), level 4
+// (1 MiB per team), level 4 on the block-chain path (2 MiB per slice, no epochs)
+struct table_part { dev_buf<u32> tables, epochs; u32 teams = 0; size_t bytes() const { return tables.bytes + epochs.bytes; } };
+// zstd levels 5 .. 10 (and level 4 up to 16 KiB): the sorted positions (KLazyRec), where each stands, the parse order (optional)
+struct lazy_part { dev_buf<u32> srt, wr, order; u32 pos_cap = 0, chunk = 0; size_t bytes() const { return srt.bytes + wr.bytes + order.bytes; } };
+// the dictionary of the last kmp_zstd_compress_batch_dict call: content, CDict tables (built on the host), a formatted one's tables
+struct dict_part {
+    dev_buf<u8> content; dev_buf<u32> L, S; dev_buf<KDictPrior> prior;
+    u32 size = 0, content_size = 0; u64 hash = 0; u32 W = 0, H = 0, C = 0, M = 0; u32 rep[2] = { 0, 0 };
+    size_t bytes() const { return content.bytes + L.bytes + S.bytes + prior.bytes; }
+};
+// ... for the decoder: the caller's dictionary lies in device memory, its head is read back once per dictionary
+struct ddict_part {
+    dev_buf<KDictDPrior> prior; const void* ptr = nullptr; u32 size = 0; u64 hash = 0; u32 off = 0, id = 0, rep[3] = { 0, 0, 0 };
+    size_t bytes() const { return prior.bytes; }
+};
+// decoder staging: sequences decoded ahead of k_zstd_decode (+ the size sort's keys, permutation and buckets), literals
+struct pre_seq_part { dev_buf<u64> stage; dev_buf<KPreBlk> blk; dev_buf<u32> nblk, sort; u32 seq_cap = 0; size_t bytes() const { return stage.bytes + blk.bytes + nblk.bytes + sort.bytes; } };
+struct pre_lit_part { dev_buf<u8> lits; dev_buf<KPreLit> rec; dev_buf<u32> nrec; u32 lit_cap = 0; size_t bytes() const { return lits.bytes + rec.bytes + nrec.bytes; } };
+// the raw-deflate workspace, two halves of `chunk` slices each
+struct dfl_lazy_part {
+    dev_buf<u16> link; dev_buf<KdBest> best; dev_buf<u32> syms, wr, order;
+    dev_buf<u16> rank; dev_buf<u32> state, maxlen;                 // slices above 64 KiB (deflate_lazy.h, segments): the sort's ranks, the parse's state between segments, the batch's longest slice
+    hip_stream sort_st[2]; hip_event sorted[2][2], parsed[2][2];   // ... a sort stream per half; span arrays in two copies (parity of the segment): sorted / parsed events
+    dev_buf<KdSliceMeta> meta; dev_buf<KdBlockInfo> blocks;
+    hip_event searched[2], done[2];
+    u32 chunk = 0, pos_cap = 0, blk_cap = 0;                         // slices per half, positions / blocks per slice
+    size_t bytes() const { return link.bytes + best.bytes + syms.bytes + wr.bytes + order.bytes + rank.bytes + state.bytes + maxlen.bytes + meta.bytes + blocks.bytes; }
+};
+// levels 1 .. 3: symbols / blocks of 4 * chunk slices (one piece)
+struct dfl_fast_part { dev_buf<u32> syms; dev_buf<KdSliceMeta> meta; dev_buf<KdBlockInfo> blocks; size_t bytes() const { return syms.bytes + meta.bytes + blocks.bytes; } };
+
+// --------------------------------------------------------------------------
 // batch context
 // --------------------------------------------------------------------------
 enum { KMP_MAX_CHUNKS = 4, KMP_MAX_PIECES = 8 };
+struct kmp_span { hip_event start, end; };                 // a timed stretch of one stream (kmp_batch_set_profiling)
 struct kmp_batch_ctx {
-    int device; u32 max_slices, max_slice_bytes; int G; int team_fixed; int table_retry = 0; u32 match_blocks, match_blocks_l3, nteams, l3_team_slots;
-    u32 seq_cap, lit_cap, scratch_words;
-    KSeq* seqs; u8* lits; KSliceMeta* meta; u32* scratch; u32* tables; u32* team_epoch; u32* counter;
-    int profiling; hipEvent_t ev[14]; int ev_valid[7];
-    // zstd compress pipeline: entropy coding of chunk i (second stream) runs beside the match kernel of chunk i+1
+    int device = 0; u32 max_slices = 0, max_slice_bytes = 0; int G = 0; int team_fixed = 0; int table_retry = 0; u32 match_blocks = 0, match_blocks_l3 = 0, nteams = 0, l3_team_slots = 0;
+    u32 seq_cap = 0, lit_cap = 0, scratch_words = 0;
+    // the workspace: one arena (which holds seqs / lits / meta / scratch and the table pieces) or, without one, separate buffers;
+    // the plain pointers are views into whichever holds them
+    dev_buf<u8> arena;
+    dev_buf<KSeq> seqs_buf; dev_buf<u8> lits_buf; dev_buf<KSliceMeta> meta_buf; dev_buf<u32> scratch_buf, tables_buf;
+    KSeq* seqs = nullptr; u8* lits = nullptr; KSliceMeta* meta = nullptr; u32* scratch = nullptr; u32* tables = nullptr;
+    u32* tseg[4] = { nullptr, nullptr, nullptr, nullptr }; u32 tseg_n = 0;       // the team tables in four pieces spread over the arena (or tseg_n == 1: tables alone)
+    dev_buf<u32> team_epoch, counter;
+    dev_buf<u32> len_ok, d_status;                // sanitised slice lengths of the running batch; status word (KMP_STATUS_*)
+    u32 table_layout = 0;                         // which of the arena's layouts holds the table pieces (1 .. 8; 0: no arena)
+    float place_ms = 0; u32 place_tried = 0;      // the team tables' placement: probe time of the region kept, candidates tried
+    float table_reads_per_s = 0, table_pairs_per_s = 0;     // random loads / load + store pairs per second over this context's team tables (k_table_probe at creation; 0 = not measured)
     // level 3, batches of more than half the team slots: one launch of each kernel or two chunks?  Tried once each on the
     // context's first two such batches (whole-step HIP events), then the faster stays -- the parse kernel's time differs
     // by 17 % between runs of the same box, and which setting wins depends on it.
-    u32* tables_flat; u32* team_epoch_flat;     // levels 1 / 2 and the dictionary parser: one piece (they wait for latency and are slower over spread tables), allocated on first use when the level-3 tables are spread
-    u32* tseg[4]; u32 tseg_n;                   // the team tables in four pieces spread over the context's arena (or tseg_n == 1: tables alone)
-    u32* tables4 = nullptr; u32* epoch4 = nullptr; u32 teams4 = 0;      // level 4's table set (1 MiB per team), allocated by the first level-4 batch
-    u32* big_tables4 = nullptr;                 // ... and on the block-chain path: 2 MiB per slice (2^18 + 2^18 entries)
-    u32 table_layout;                           // which of the arena's layouts holds the table pieces (1 .. 8; 0: no arena)
-    u8* arena; size_t arena_bytes;              // one allocation that holds seqs / lits / meta / scratch and the table pieces (else null: separate allocations)
-    float place_ms; u32 place_tried;            // the team tables' placement: probe time of the region kept, candidates tried
-    float table_reads_per_s, table_pairs_per_s; // random loads / load + store pairs per second over this context's team tables (k_table_probe at creation; 0 = not measured)
-    int tune_state; int tune_pending; u32 tune_pick; float tune_ms[2]; hipEvent_t tune_ev[2];
-    hipStream_t st2; hipEvent_t evm[KMP_MAX_CHUNKS][2], eve[KMP_MAX_CHUNKS][2], ev_join, ev_last_match; int have_last_match; u32 last_chunks;
-    hipEvent_t ev_pre[KMP_MAX_CHUNKS + 1];      // decoder: [0] where the caller's stream stands, [1 + i] piece i pre-decoded
-    // raw-deflate workspace, allocated on first use, for dfl_chunk slices at a time
-    u32 dfl_chunk; u16* dfl_link; KdBest* dfl_best; u32* dfl_syms; KdSliceMeta* dfl_meta; u32* dfl_wr; u32* dfl_order;      // two halves of dfl_chunk slices each
-    u32* dfl_fsyms; KdSliceMeta* dfl_fmeta; KdBlockInfo* dfl_fblocks; int dfl_ftried;          // levels 1 .. 3: symbols / blocks of 4 * dfl_chunk slices (one piece)
-    hipStream_t dfl_sort_st[2]; hipEvent_t dfl_sorted[2][2], dfl_parsed[2][2]; int dfl_seg_sync;   // ... a sort stream per workspace half; span arrays in two copies (parity of the segment): sorted / parsed events
-    u16* dfl_rank; u32* dfl_state; u32* dfl_maxlen;                                             // slices above 64 KiB (deflate_lazy.h, segments): the sort's ranks, the parse's state between segments, the batch's longest slice
-    u32 dfl_pos_cap, dfl_blk_cap; KdBlockInfo* dfl_blocks;                                      // positions / blocks per slice in them
-    hipEvent_t dfl_searched[2], dfl_done[2]; int dfl_events;
+    int tune_state = 0; int tune_pending = 0; u32 tune_pick = 0; float tune_ms[2] = { 0, 0 }; kmp_span tune;
+    // zstd compress pipeline: entropy coding of chunk i (second stream) runs beside the match kernel of chunk i+1
+    hip_stream st2; hip_event ev_join; u32 last_chunks = 0;
+    hip_event ev_pre[KMP_MAX_CHUNKS + 1];         // decoder: [0] where the caller's stream stands, [1 + i] piece i pre-decoded
+    // profiling: each group of named events with its own valid flag.  match[i].end also marks where chunk i's entropy launch may start.
+    int profiling = 0;
+    kmp_span match[KMP_MAX_CHUNKS], entropy[KMP_MAX_CHUNKS]; u32 timed_chunks = 0; int zstd_timed = 0;
+    kmp_span decode_t; int decode_timed = 0;
+    kmp_span deflate_t; int deflate_timed = 0;
+    struct { hip_event chains, best, best_done, parse, encode, encode_done; } dfl_mark; int dfl_marked = 0;   // the first piece's stages (kmp_deflate_last_kernel_ms)
+    // the parts added on first use (null: absent)
+    std::unique_ptr<table_part> flat, t4, chain_t4;
+    std::unique_ptr<lazy_part> lz;
+    std::unique_ptr<dict_part> dict;
+    std::unique_ptr<ddict_part> ddict;
+    std::unique_ptr<pre_seq_part> pre_seq; std::unique_ptr<pre_lit_part> pre_lit;
+    u32 pre_slices = 0, pre_blk_cap = 0; int pre_tried = 0;      // entries the staging holds (a larger batch is decoded in pieces); pre_tried: do not try again
+    std::unique_ptr<dfl_lazy_part> dfl; std::unique_ptr<dfl_fast_part> dflf; int dfl_ftried = 0;
     // frames of several blocks (max_slice_bytes above 128 KiB): per-slice state carried between the block rounds
-    // raw-content dictionary of the last kmp_zstd_compress_batch_dict call: device copy + CDict tables (built on the host)
-    u8* d_dict; u32* d_dictL; u32* d_dictS; u32 dict_size; u64 dict_hash; u32 cdW, cdH, cdC, cdM;
-    struct KDictDPrior* d_dprior; const void* ddict_ptr; u32 ddict_size; u64 ddict_hash; u32 ddict_off, ddict_id, ddict_rep[3];      // ... for the decoder (the caller's dictionary lies in device memory: its head is read back once per dictionary)
-    u32* lz_srt; u32* lz_wr; u32* lz_order; u32 lz_pos_cap, lz_chunk;       // zstd levels 5 .. 10 (and level 4's slices up to 16 KiB): the sorted positions' records (KLazyRec, 16 bytes), where each position stands (one piece's worth)
-    struct KDictPrior* d_prior; u32 dict_content; u32 dict_rep[2];      // a formatted dictionary: its tables on the device, the size of its content part, its repeat offsets
-    int big; int big_G; KFrameState* fstate; u32* hufct; u32* big_tables; u32* remaining; u32* big_counters; u32 last_rounds;
-    u32 cus;                                   // compute units of the device
-    // decoder: sequences decoded ahead of k_zstd_decode (allocated on first use; pre_tried: do not try again)
-    u64* pre_stage; KPreBlk* pre_blk; u32* pre_nblk; u32 pre_seq_cap, pre_blk_cap; int pre_tried;
-    u32 pre_slices;                             // entries the staging areas hold (a larger batch is decoded in pieces)
-    u32* pre_sort;                              // per staged entry: key, slot -> entry map; then 256 bucket counters
-    u8* pre_lits; KPreLit* pre_lit; u32* pre_nlit; u32 pre_lit_cap;
-    u32* len_ok; u32* d_status;                // sanitised slice lengths of the running batch; status word (KMP_STATUS_*)
+    int big = 0; int big_G = 0; dev_buf<KFrameState> fstate; dev_buf<u32> hufct, big_tables, remaining, big_counters; u32 last_rounds = 0;
+    u32 cus = 0;                                  // compute units of the device
     // one batch at a time per context: a batch queued on another stream waits for the previous one's last kernel
-    hipEvent_t ev_done; int have_done;
+    hip_event ev_done; int have_done = 0;
     // ... or its pieces did, each on a stream of its own (kmp_zstd_compress_batch_pieces): the next batch waits for all of them
-    hipEvent_t ev_piece[KMP_MAX_PIECES]; u32 pieces_pending;
+    hip_event ev_piece[KMP_MAX_PIECES]; u32 pieces_pending = 0;
     // experiment switches, read from the environment once, when the context is created
     struct { u32 chunks, match_flags, entropy_pad, first_permille, fast_first_permille, entropy_flags, decode_flags, decode_pad, big_rounds, big_spw,
-                 dfl_chunk, dfl_chain_waves, dfl_serial, dfl_flags, decode_pre, decode_sort, decode_pieces, decode_stage_slices, inflate_pre, inflate_pieces, autotune, match_v2, fuse; } knob;
+                 dfl_chunk, dfl_chain_waves, dfl_serial, dfl_flags, decode_pre, decode_sort, decode_pieces, decode_stage_slices, inflate_pre, inflate_pieces, autotune, match_v2, fuse; } knob = {};
 };
+
+// a context's owner (the host engines, the streaming contexts): kmp_batch_destroy on the context's device
+struct batch_deleter { void operator()(kmp_batch_ctx* c) const { kmp_batch_destroy(c); } };
+using batch_ptr = std::unique_ptr<kmp_batch_ctx, batch_deleter>;
 
 // --------------------------------------------------------------------------
 // host functions shared between the translation units
@@ -120,7 +221,18 @@ int size_sort(kmp_batch_ctx* c, hipStream_t st, const u8* src, const u64* in_off
 int pieces_begin(kmp_batch_ctx* c, u32 pieces, void* const* hip_streams);
 int piece_enqueue(kmp_batch_ctx* c, u32 p, u32 pieces, const void* d_src, const uint64_t* d_in_off, const uint32_t* d_in_len, uint32_t n,
                   void* d_dst, const uint64_t* d_out_off, uint32_t* d_out_len, hipStream_t st);
-void pieces_end(kmp_batch_ctx* c, u32 pieces);
+// The end of a batch in pieces, on every way out once pieces_begin has succeeded: the pieces not queued (p >= queued) mark where
+// their streams stand, and the next batch waits for every piece.  The batch's kernel timings are not the per-chunk ones.
+struct pieces_end {
+    kmp_batch_ctx* c; u32 pieces; void* const* streams; u32 queued;
+    pieces_end(pieces_end const&) = delete;
+    pieces_end& operator=(pieces_end const&) = delete;
+    ~pieces_end()
+    {
+        for (u32 p = queued; p < pieces; p++) (void)hipEventRecord(c->ev_piece[p], (hipStream_t)streams[p]);
+        c->have_done = 0; c->pieces_pending = pieces; c->last_chunks = pieces; c->zstd_timed = 0;
+    }
+};
 // frames out of the strided device layout straight into registered host memory (device-visible address h_dst_dev)
 int scatter_frames(kmp_batch_ctx* c, hipStream_t st, const u8* d_src, const u64* d_in_off, u32* d_len, u32 n, u8* h_dst_dev, const u64* d_h_off, const u32* d_h_cap, u32* d_status);
 // frames of several blocks (kmp_batch.hip); stream: KFrameArgs.stream

@@ -65,56 +65,45 @@ extern "C" const char* kmp_zstd_get_error_name(size_t code)
     }
 }
 
-// device staging shared by the two stream contexts
+// device staging shared by the two stream contexts (the context goes first: its destruction selects its device for the buffers)
 struct stream_dev {
-    kmp_batch_ctx* batch; u8* d_in; u8* d_out; u64* d_off; u32* d_len; size_t in_cap, out_cap; u32 tier;
+    dev_buf<u8> d_in, d_out; dev_buf<u64> d_off; dev_buf<u32> d_len; size_t in_cap = 0, out_cap = 0; u32 tier = 0; batch_ptr batch;
 };
 // the staging buffers live on the device the context was first used on: later calls may come from a thread whose
 // current device is another one (the reference frees contexts on a cleaner thread, Cleaner.jvm.kt:23-36)
 static bool stream_dev_select(const stream_dev& s) { return !s.batch || hipSetDevice(s.batch->device) == hipSuccess; }
-static void stream_dev_free(stream_dev& s);
 // staging for one slice / frame of at most `bytes` on either side: the 128 KiB tier first, the 2 MiB tier
-// (frames of several blocks) when a larger one shows up
+// (frames of several blocks) when a larger one shows up; `s` is empty when this fails
 // (level 1 above 128 KiB wants a context of exactly its 512 KiB window: `exact` = that tier)
 static size_t stream_dev_init(stream_dev& s, size_t bytes = 0, u32 exact = 0)
 {
     if (s.batch && exact && s.tier == exact) return 0;
     if (s.batch && !exact && bytes + 1024 <= s.in_cap) return 0;
-    if (s.batch) stream_dev_free(s);
+    if (s.batch) { s.batch.reset(); s = stream_dev(); }
     // 128 KiB, 2 MiB, then the next power of two that holds the slice
     u32 tier = exact ? exact : (bytes <= KMP_MAX_SLICE_BYTES) ? KMP_MAX_SLICE_BYTES : (2u << 20);
     while (!exact && (size_t)tier < bytes && tier < KMP_MAX_BIG_SLICE_BYTES) tier <<= 1;
-    s.tier = tier;
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) return KERRC(ZE_GENERIC);          // the caller's current device, as a libzstd context lives where its caller runs
-    if (kmp_batch_create(&s.batch, dev, 1, tier, 8) != KMP_OK) return KERRC(ZE_memory_allocation);
-    s.in_cap = tier + (tier >> 7) + 1024; s.out_cap = tier + (tier >> 7) + 1024;
-    if (hipMalloc((void**)&s.d_in, s.in_cap) != hipSuccess || hipMalloc((void**)&s.d_out, s.out_cap) != hipSuccess ||
-        hipMalloc((void**)&s.d_off, 64) != hipSuccess || hipMalloc((void**)&s.d_len, 64) != hipSuccess) return KERRC(ZE_memory_allocation);
+    stream_dev n; kmp_batch_ctx* b = nullptr;
+    if (kmp_batch_create(&b, dev, 1, tier, 8) != KMP_OK) return KERRC(ZE_memory_allocation);
+    n.batch.reset(b); n.tier = tier;
+    n.in_cap = tier + (tier >> 7) + 1024; n.out_cap = tier + (tier >> 7) + 1024;
+    if (n.d_in.alloc(n.in_cap) != KMP_OK || n.d_out.alloc(n.out_cap) != KMP_OK || n.d_off.alloc(64) != KMP_OK || n.d_len.alloc(64) != KMP_OK) return KERRC(ZE_memory_allocation);
+    s = std::move(n);
     return 0;
-}
-static void stream_dev_free(stream_dev& s)
-{
-    if (s.batch) { (void)hipSetDevice(s.batch->device); kmp_batch_destroy(s.batch); (void)hipFree(s.d_in); (void)hipFree(s.d_out); (void)hipFree(s.d_off); (void)hipFree(s.d_len); }
-    memset(&s, 0, sizeof(s));
 }
 
 struct kmp_zstd_cctx {
-    int level; std::vector<u8> in; std::vector<u8> out; size_t out_pos; int stage;   // 0 = collecting, 1 = flushing
+    int level = 3; std::vector<u8> in; std::vector<u8> out; size_t out_pos = 0; int stage = 0;   // 0 = collecting, 1 = flushing
     stream_dev dev;
     std::vector<u8> dict;                       // raw-content dictionary (ZSTD_CCtx_loadDictionary keeps a copy too)
-    size_t fed_continue;                        // bytes that arrived with ZSTD_e_continue: > 0 makes it a streaming frame
-    int end_was_empty;                          // the closing calls brought no data
+    size_t fed_continue = 0;                    // bytes that arrived with ZSTD_e_continue: > 0 makes it a streaming frame
+    int end_was_empty = 0;                      // the closing calls brought no data
 };
 
-extern "C" kmp_zstd_cctx* kmp_zstd_create_cctx(void)
-{
-    kmp_zstd_cctx* c = new (std::nothrow) kmp_zstd_cctx();
-    if (!c) return nullptr;
-    c->level = 3; c->out_pos = 0; c->stage = 0; memset(&c->dev, 0, sizeof(c->dev)); c->fed_continue = 0; c->end_was_empty = 0;
-    return c;
-}
-extern "C" size_t kmp_zstd_free_cctx(kmp_zstd_cctx* c) { if (c) { stream_dev_free(c->dev); delete c; } return 0; }
+extern "C" kmp_zstd_cctx* kmp_zstd_create_cctx(void) { return new (std::nothrow) kmp_zstd_cctx(); }
+extern "C" size_t kmp_zstd_free_cctx(kmp_zstd_cctx* c) { delete c; return 0; }
 extern "C" size_t kmp_zstd_cctx_set_parameter(kmp_zstd_cctx* c, int param, int value)
 {
     if (!c) return KERRC(ZE_GENERIC);
@@ -181,26 +170,26 @@ static size_t run_single_compress(kmp_zstd_cctx* c, size_t first_room, size_t en
         if (tail_direct) {
             bool const neg = c->level < 0;
             u32 const strategy = (c->level == 3 || c->level == 4) ? 0u : neg ? 1u : (u32)c->level;
-            if (zstd_compress_big(s.batch, s.d_in, s.d_off, s.d_len, 1, s.d_out, s.d_off + 1, s.d_len + 1, nullptr, 1u, strategy, tail_direct, neg ? (u32)(1 - c->level) : 0u, c->level == 4) != KMP_OK) return KERRC(ZE_GENERIC);
+            if (zstd_compress_big(s.batch.get(), s.d_in, s.d_off, s.d_len, 1, s.d_out, s.d_off + 1, s.d_len + 1, nullptr, 1u, strategy, tail_direct, neg ? (u32)(1 - c->level) : 0u, c->level == 4) != KMP_OK) return KERRC(ZE_GENERIC);
         } else
-        if (kmp_zstd_compress_batch_stream_level(s.batch, s.d_in, s.d_off, s.d_len, 1, s.d_out, s.d_off + 1, s.d_len + 1, c->end_was_empty, c->level, nullptr) != KMP_OK) return KERRC(ZE_GENERIC);
+        if (kmp_zstd_compress_batch_stream_level(s.batch.get(), s.d_in, s.d_off, s.d_len, 1, s.d_out, s.d_off + 1, s.d_len + 1, c->end_was_empty, c->level, nullptr) != KMP_OK) return KERRC(ZE_GENERIC);
     } else
     if (n > KMP_MAX_SLICE_BYTES && !in_place && c->dict.empty() && (c->level == 3 || c->level == 4 || l1big)) {
         // the reference's one-shot driver above 128 KiB: staged input
-        if (kmp_zstd_compress_batch_reference(s.batch, s.d_in, s.d_off, s.d_len, 1, s.d_out, s.d_off + 1, s.d_len + 1, c->level, (u32)first_room, nullptr) != KMP_OK) return KERRC(ZE_GENERIC);
+        if (kmp_zstd_compress_batch_reference(s.batch.get(), s.d_in, s.d_off, s.d_len, 1, s.d_out, s.d_off + 1, s.d_len + 1, c->level, (u32)first_room, nullptr) != KMP_OK) return KERRC(ZE_GENERIC);
     } else
     if (c->level != 3) {
         if (!c->dict.empty()) return KERRC(ZE_parameter_unsupported);   // levels 1 / 2: no dictionary
-        if (kmp_zstd_compress_batch_level(s.batch, s.d_in, s.d_off, s.d_len, 1, s.d_out, s.d_off + 1, s.d_len + 1, c->level, nullptr) != KMP_OK) return KERRC(ZE_GENERIC);
+        if (kmp_zstd_compress_batch_level(s.batch.get(), s.d_in, s.d_off, s.d_len, 1, s.d_out, s.d_off + 1, s.d_len + 1, c->level, nullptr) != KMP_OK) return KERRC(ZE_GENERIC);
     } else
     if (!c->dict.empty()) {
         if (n > KMP_MAX_SLICE_BYTES) return KERRC(ZE_srcSize_wrong);          // frames of several blocks with a dictionary: CPU library
-        if (kmp_zstd_compress_batch_dict(s.batch, s.d_in, s.d_off, s.d_len, 1, s.d_out, s.d_off + 1, s.d_len + 1,
+        if (kmp_zstd_compress_batch_dict(s.batch.get(), s.d_in, s.d_off, s.d_len, 1, s.d_out, s.d_off + 1, s.d_len + 1,
                                          c->dict.data(), (u32)c->dict.size(), nullptr) != KMP_OK) {
             return dict_header_state(c->dict.data(), c->dict.size(), 0) < 0 ? KERRC(ZE_dictionary_corrupted) : KERRC(ZE_GENERIC);
         }
     } else
-    if (kmp_zstd_compress_batch(s.batch, s.d_in, s.d_off, s.d_len, 1, s.d_out, s.d_off + 1, s.d_len + 1, nullptr) != KMP_OK) return KERRC(ZE_GENERIC);
+    if (kmp_zstd_compress_batch(s.batch.get(), s.d_in, s.d_off, s.d_len, 1, s.d_out, s.d_off + 1, s.d_len + 1, nullptr) != KMP_OK) return KERRC(ZE_GENERIC);
     if (hipMemcpy(&olen, s.d_len + 1, 4, hipMemcpyDeviceToHost) != hipSuccess) return KERRC(ZE_GENERIC);
     if (olen == 0 || olen > s.out_cap) return KERRC(ZE_GENERIC);
     c->out.resize(olen);
@@ -254,10 +243,9 @@ extern "C" kmp_zlib_cstream* kmp_zlib_create_compressor(int level, int window_bi
     kmp_zlib_cstream* z = new (std::nothrow) kmp_zlib_cstream();
     if (!z) return nullptr;
     z->level = level; z->window_bits = window_bits; z->mem_level = mem_level; z->strategy = strategy; z->out_pos = 0; z->stage = 0;
-    memset(&z->dev, 0, sizeof(z->dev));
     return z;
 }
-extern "C" int kmp_zlib_free_compressor(kmp_zlib_cstream* z) { if (z) { stream_dev_free(z->dev); delete z; } return 0; }
+extern "C" int kmp_zlib_free_compressor(kmp_zlib_cstream* z) { delete z; return 0; }
 
 extern "C" int kmp_zlib_compress_stream(kmp_zlib_cstream* z, void* dst, size_t dst_size, size_t* dst_pos,
                                         const void* src, size_t src_size, size_t* src_pos, int finish)
@@ -280,7 +268,7 @@ extern "C" int kmp_zlib_compress_stream(kmp_zlib_cstream* z, void* dst, size_t d
         if (len && hipMemcpy(s.d_in, z->in.data(), len, hipMemcpyHostToDevice) != hipSuccess) return Z_MEM_ERROR_;
         if (hipMemcpy(s.d_off, offs, sizeof(offs), hipMemcpyHostToDevice) != hipSuccess) return Z_MEM_ERROR_;
         if (hipMemcpy(s.d_len, &len, 4, hipMemcpyHostToDevice) != hipSuccess) return Z_MEM_ERROR_;
-        if (deflate_batch_impl(s.batch, s.d_in, s.d_off, s.d_len, 1, s.d_out, s.d_off + 1, s.d_len + 1, (u32)wrap, nullptr, z->level, wb, z->mem_level) != KMP_OK) return Z_MEM_ERROR_;
+        if (deflate_batch_impl(s.batch.get(), s.d_in, s.d_off, s.d_len, 1, s.d_out, s.d_off + 1, s.d_len + 1, (u32)wrap, nullptr, z->level, wb, z->mem_level) != KMP_OK) return Z_MEM_ERROR_;
         if (hipMemcpy(&olen, s.d_len + 1, 4, hipMemcpyDeviceToHost) != hipSuccess) return Z_MEM_ERROR_;
         if (olen == 0 || olen > s.out_cap) return Z_DATA_ERROR_;
         z->out.resize(olen);
@@ -294,7 +282,7 @@ extern "C" int kmp_zlib_compress_stream(kmp_zlib_cstream* z, void* dst, size_t d
     return k ? Z_OK_ : Z_BUF_ERROR_;
 }
 
-struct kmp_zlib_dstream { int window_bits; std::vector<u8> in; std::vector<u8> out; size_t out_pos; int stage; kmp_batch_ctx* batch; };
+struct kmp_zlib_dstream { int window_bits; std::vector<u8> in; std::vector<u8> out; size_t out_pos; int stage; batch_ptr batch; };
 
 extern "C" kmp_zlib_dstream* kmp_zlib_create_decompressor(int window_bits)
 {
@@ -304,10 +292,10 @@ extern "C" kmp_zlib_dstream* kmp_zlib_create_decompressor(int window_bits)
     if (!raw && !zl && !gz && !any) return nullptr;
     kmp_zlib_dstream* z = new (std::nothrow) kmp_zlib_dstream();
     if (!z) return nullptr;
-    z->window_bits = window_bits; z->out_pos = 0; z->stage = 0; z->batch = nullptr;
+    z->window_bits = window_bits; z->out_pos = 0; z->stage = 0;
     return z;
 }
-extern "C" int kmp_zlib_free_decompressor(kmp_zlib_dstream* z) { if (z) { if (z->batch) kmp_batch_destroy(z->batch); delete z; } return 0; }
+extern "C" int kmp_zlib_free_decompressor(kmp_zlib_dstream* z) { delete z; return 0; }
 
 extern "C" int kmp_zlib_decompress_stream(kmp_zlib_dstream* z, void* dst, size_t dst_size, size_t* dst_pos,
                                           const void* src, size_t src_size, size_t* src_pos, int finish)
@@ -319,23 +307,23 @@ extern "C" int kmp_zlib_decompress_stream(kmp_zlib_dstream* z, void* dst, size_t
         if (avail) { const u8* p = (const u8*)src + *src_pos; z->in.insert(z->in.end(), p, p + avail); *src_pos = src_size; }
         if (!finish) return avail ? Z_OK_ : Z_BUF_ERROR_;           // the stream is decoded when the caller finishes it
         if (!z->batch) {
-            int dev = 0;
-            if (hipGetDevice(&dev) != hipSuccess || kmp_batch_create(&z->batch, dev, 1, 65536, 8) != KMP_OK) return Z_MEM_ERROR_;
+            int dev = 0; kmp_batch_ctx* b = nullptr;
+            if (hipGetDevice(&dev) != hipSuccess || kmp_batch_create(&b, dev, 1, 65536, 8) != KMP_OK) return Z_MEM_ERROR_;
+            z->batch.reset(b);
         }
         size_t const n = z->in.size();
-        u8* d_in = nullptr; u8* d_out = nullptr; u64* d_off = nullptr; u32* d_len = nullptr; int rc = Z_MEM_ERROR_;
-        if (hipMalloc((void**)&d_in, n + 64) == hipSuccess && hipMalloc((void**)&d_off, 64) == hipSuccess && hipMalloc((void**)&d_len, 64) == hipSuccess) {
+        dev_buf<u8> d_in, d_out; dev_buf<u64> d_off; dev_buf<u32> d_len; int rc = Z_MEM_ERROR_;
+        if (d_in.alloc(n + 64) == KMP_OK && d_off.alloc(64) == KMP_OK && d_len.alloc(64) == KMP_OK) {
             // the decoded size is not known in advance: grow the capacity until the stream fits
             for (size_t cap = 256u << 10; cap <= (256u << 20); cap <<= 2) {
-                if (d_out) { (void)hipFree(d_out); d_out = nullptr; }
-                if (hipMalloc((void**)&d_out, cap + 64) != hipSuccess) break;
+                if (d_out.alloc(cap + 64) != KMP_OK) break;
                 u64 offs[2] = { 0, 0 }; u32 lens[4] = { (u32)n, (u32)cap, 0, 0 };
                 if ((n && hipMemcpy(d_in, z->in.data(), n, hipMemcpyHostToDevice) != hipSuccess) ||
                     hipMemcpy(d_off, offs, sizeof(offs), hipMemcpyHostToDevice) != hipSuccess ||
                     hipMemcpy(d_len, lens, sizeof(lens), hipMemcpyHostToDevice) != hipSuccess) break;
                 // (the window declared for a zlib stream bounds what its header may name: inflate.c, "invalid window size")
                 int const zw = z->window_bits >= 40 ? z->window_bits - 32 : (z->window_bits >= 8 && z->window_bits <= 15) ? z->window_bits : 0;
-                if (inflate_batch_impl(z->batch, d_in, d_off, d_len, 1, d_out, d_off + 1, d_len + 1, d_len + 2, (int32_t*)(d_len + 3),
+                if (inflate_batch_impl(z->batch.get(), d_in, d_off, d_len, 1, d_out, d_off + 1, d_len + 1, d_len + 2, (int32_t*)(d_len + 3),
                                        z->window_bits < 0 ? 0 : (z->window_bits <= 15 ? 1 : (z->window_bits <= 31 ? 2 : 3)), zw, nullptr) != KMP_OK) break;
                 if (hipMemcpy(lens, d_len, sizeof(lens), hipMemcpyDeviceToHost) != hipSuccess) break;
                 int const st = (int)lens[3];
@@ -347,7 +335,6 @@ extern "C" int kmp_zlib_decompress_stream(kmp_zlib_dstream* z, void* dst, size_t
                 break;
             }
         }
-        (void)hipFree(d_in); (void)hipFree(d_out); (void)hipFree(d_off); (void)hipFree(d_len);
         if (rc != Z_OK_) return rc == Z_MEM_ERROR_ ? Z_MEM_ERROR_ : Z_DATA_ERROR_;
         z->stage = 1; z->out_pos = 0;
     }
@@ -359,25 +346,20 @@ extern "C" int kmp_zlib_decompress_stream(kmp_zlib_dstream* z, void* dst, size_t
 }
 
 struct kmp_zstd_dctx {
-    std::vector<u8> in; std::vector<u8> out; size_t out_pos; int stage;   // 0 = collecting a frame, 1 = flushing
-    stream_dev dev; u32* d_status;
-    std::vector<u8> dict; u8* d_dict;                  // raw-content dictionary (ZSTD_DCtx_loadDictionary), host copy + device copy
+    std::vector<u8> in; std::vector<u8> out; size_t out_pos = 0; int stage = 0;   // 0 = collecting a frame, 1 = flushing
+    dev_buf<u32> d_status;
+    std::vector<u8> dict; dev_buf<u8> d_dict;          // raw-content dictionary (ZSTD_DCtx_loadDictionary), host copy + device copy
+    stream_dev dev;                                    // (last: freed first, and its context selects its device for the buffers above)
 };
 
-extern "C" kmp_zstd_dctx* kmp_zstd_create_dctx(void)
-{
-    kmp_zstd_dctx* d = new (std::nothrow) kmp_zstd_dctx();
-    if (!d) return nullptr;
-    d->out_pos = 0; d->stage = 0; memset(&d->dev, 0, sizeof(d->dev)); d->d_status = nullptr; d->d_dict = nullptr;
-    return d;
-}
-extern "C" size_t kmp_zstd_free_dctx(kmp_zstd_dctx* d) { if (d) { stream_dev_free(d->dev); if (d->d_dict) (void)hipFree(d->d_dict); if (d->d_status) (void)hipFree(d->d_status); delete d; } return 0; }
+extern "C" kmp_zstd_dctx* kmp_zstd_create_dctx(void) { return new (std::nothrow) kmp_zstd_dctx(); }
+extern "C" size_t kmp_zstd_free_dctx(kmp_zstd_dctx* d) { delete d; return 0; }
 extern "C" size_t kmp_zstd_dctx_load_dictionary(kmp_zstd_dctx* d, const void* dict, size_t dict_size)
 {
     if (!d) return KERRC(ZE_GENERIC);
     // raw-content dictionary: its bytes are the history before every frame decoded by this context (Wrapper.cpp:58-73)
     if (d->stage != 0 || !d->in.empty()) return KERRC(ZE_stage_wrong);
-    if (d->d_dict) { (void)hipFree(d->d_dict); d->d_dict = nullptr; }
+    d->d_dict.reset();
     d->dict.clear();
     if (dict == nullptr || dict_size == 0) return 0;
     if (dict_size > (8u << 20)) return KERRC(ZE_memory_allocation);
@@ -385,7 +367,7 @@ extern "C" size_t kmp_zstd_dctx_load_dictionary(kmp_zstd_dctx* d, const void* di
     // failed allocation: ZSTD_DCtx_loadDictionary -> ZSTD_createDDict_advanced returns NULL)
     if (dict_header_state((const u8*)dict, dict_size, 1) < 0) return KERRC(ZE_memory_allocation);
     d->dict.assign((const u8*)dict, (const u8*)dict + dict_size);
-    if (hipMalloc((void**)&d->d_dict, dict_size + 64) != hipSuccess) { d->d_dict = nullptr; d->dict.clear(); return KERRC(ZE_memory_allocation); }
+    if (d->d_dict.alloc(dict_size + 64, "hipMalloc(dictionary)") != KMP_OK) { d->dict.clear(); return KERRC(ZE_memory_allocation); }
     if (hipMemcpy(d->d_dict, d->dict.data(), dict_size, hipMemcpyHostToDevice) != hipSuccess) return KERRC(ZE_GENERIC);
     return 0;
 }
@@ -466,7 +448,7 @@ extern "C" size_t kmp_zstd_decompress_stream(kmp_zstd_dctx* d, void* dst, size_t
             }
             (void)hipGetLastError(); d->out.clear();                 // fall through: decode alone
         }
-        if (!d->d_status && hipMalloc((void**)&d->d_status, 64) != hipSuccess) return KERRC(ZE_memory_allocation);
+        if (!d->d_status && d->d_status.alloc(64, "hipMalloc(status words)") != KMP_OK) return KERRC(ZE_memory_allocation);
         u32 res[2] = { 0, 0 };
         // content size in the header: staged for exactly that; none (streaming frames): for 4 x the frame (2 MiB at least),
         // and again for 4 x as much while the decoder answers "destination too small", up to the 1 GiB served here
@@ -482,7 +464,7 @@ extern "C" size_t kmp_zstd_decompress_stream(kmp_zstd_dctx* d, void* dst, size_t
             if (hipMemcpy(s.d_in, d->in.data(), total, hipMemcpyHostToDevice) != hipSuccess) return KERRC(ZE_GENERIC);
             if (hipMemcpy(s.d_off, offs, sizeof(offs), hipMemcpyHostToDevice) != hipSuccess) return KERRC(ZE_GENERIC);
             if (hipMemcpy(s.d_len, lens, sizeof(lens), hipMemcpyHostToDevice) != hipSuccess) return KERRC(ZE_GENERIC);
-            if (kmp_zstd_decompress_batch_dict(s.batch, s.d_in, s.d_off, s.d_len, 1, s.d_out, s.d_off + 1, s.d_len + 1,
+            if (kmp_zstd_decompress_batch_dict(s.batch.get(), s.d_in, s.d_off, s.d_len, 1, s.d_out, s.d_off + 1, s.d_len + 1,
                                                d->d_status, d->d_status + 1, d->d_dict, (u32)d->dict.size(), nullptr) != KMP_OK) return KERRC(ZE_GENERIC);
             if (hipMemcpy(res, d->d_status, 8, hipMemcpyDeviceToHost) != hipSuccess) return KERRC(ZE_GENERIC);
             if (res[1] == (u32)ZE_dstSize_tooSmall && content == (size_t)-1 && want < KMP_MAX_BIG_SLICE_BYTES) { want *= 4; continue; }
