@@ -570,9 +570,11 @@ KX_DEV u32 klit_header_raw_rle(u8* dst, u32 type, u32 litSize)
 
 // Huffman-code `lits[0..litSize)` into `op` (after the tree description of hSize
 // bytes that lane 0 already wrote at op - hSize).  Returns the stream bytes
-// (incl. jump table), 0 if a stream does not fit its 16-bit size field.
+// (incl. jump table), 0 if a stream does not fit its 16-bit size field -- or if they would come to `limit` bytes or more:
+// the callers keep a result below limit only, and nothing is written then (a table that does not fit the data -- a
+// dictionary's, used unseen -- codes a byte in up to 11 bits: more than the slot behind d_out_off holds).
 KX_DEV u32 khuf_encode_streams(KEntropyLds& lds, u8* op, const u8* lits, u32 litSize, bool single,
-                               u32* scratch, int lane)
+                               u32* scratch, int lane, u32 limit)
 {
     int const LPS = single ? 64 : 16;
     int const s = lane / LPS, j = lane % LPS;
@@ -609,6 +611,7 @@ KX_DEV u32 khuf_encode_streams(KEntropyLds& lds, u8* op, const u8* lits, u32 lit
         total = c0 + c1 + c2 + c3;
         soff = (s > 0 ? c0 : 0) + (s > 1 ? c1 : 0) + (s > 2 ? c2 : 0);
     }
+    if ((single ? total : total + 6) >= limit) return 0;          // (uniform: the sizes come from the same four lanes)
     u32 const words = (total + 3) >> 2;
     for (u32 w = (u32)lane; w < words; w += 64) scratch[w] = 0;
     kx_sync();
@@ -660,7 +663,7 @@ KX_DEV u32 kzstd_literals(KEntropyLds& lds, u8* dst, const u8* lits, u32 litSize
         // HUF_compress_internal's first heuristic: a valid old table and a small input (HUF_flags_preferRepeat): coded with it, unseen
         for (int sy = lane; sy < 256; sy += 64) lds.ct[sy] = prev->ct[sy];
         kx_sync();
-        u32 const sz = khuf_encode_streams(lds, dst + lhSize, lits, litSize, single, scratch, lane);
+        u32 const sz = khuf_encode_streams(lds, dst + lhSize, lits, litSize, single, scratch, lane, litSize - 1);
         hType = 3;
         if (sz != 0 && sz < litSize - 1) cLit = sz;
         if (cLit == 0 || cLit >= litSize - kx_min_gain(litSize)) cLit = 0;
@@ -708,7 +711,7 @@ KX_DEV u32 kzstd_literals(KEntropyLds& lds, u8* dst, const u8* lits, u32 litSize
                 if (useOld) hType = 3;
                 kx_sync();
                 if (hSize != KXE_ERR && (useOld || hSize + 12 < litSize)) {
-                    u32 const sz = khuf_encode_streams(lds, dst + lhSize + hSize, lits, litSize, single, scratch, lane);
+                    u32 const sz = khuf_encode_streams(lds, dst + lhSize + hSize, lits, litSize, single, scratch, lane, litSize - 1 - hSize);
                     if (sz != 0 && hSize + sz < litSize - 1) cLit = hSize + sz;
                 }
             }
