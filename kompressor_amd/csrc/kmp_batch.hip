@@ -6,10 +6,7 @@
 #ifdef KMP_ABLATIONS
 #include "zstd_match2.h"
 #endif
-#include "zstd_entropy.h"
-#include "zstd_match_dict.h"
-#include "zstd_lazy.h"
-#include "zstd_match_fast.h"
+#include "zstd_launch.h"            // (the compress kernels' bodies and how their arguments are built)
 #include "zstd_cdict_host.h"
 #include "zstd_decode.h"
 #include "zstd_predecode.h"
@@ -18,7 +15,6 @@
 
 #include <mutex>
 #include <new>
-#include <type_traits>
 #include <vector>
 
 // --------------------------------------------------------------------------
@@ -150,18 +146,6 @@ __global__ __launch_bounds__(256) void k_len_guard_finish(const u32* in_len, u32
     if (in_len[i] > cap) out_len[i] = 0;
     else if (meta && meta[i].status == 3u) { out_len[i] = 0; atomicOr(status, (u32)KMP_STATUS_LEVEL_SIZE); }
     else if (meta && in_len[i] >= 8 && meta[i].status != 0) { out_len[i] = 0; atomicOr(status, (u32)KMP_STATUS_KERNEL_GUARD); }
-}
-// The parsers are templates on their team width (lanes per slice): f(std::integral_constant<int, G>()) for G = 2 .. 64 (else 64)
-template <class F> static void by_team_width(int G, F const& f)
-{
-    switch (G) {
-    case 2:  f(std::integral_constant<int, 2>()); break;
-    case 4:  f(std::integral_constant<int, 4>()); break;
-    case 8:  f(std::integral_constant<int, 8>()); break;
-    case 16: f(std::integral_constant<int, 16>()); break;
-    case 32: f(std::integral_constant<int, 32>()); break;
-    default: f(std::integral_constant<int, 64>()); break;
-    }
 }
 
 // --------------------------------------------------------------------------
@@ -322,7 +306,7 @@ static int batch_create_body(kmp_batch_ctx* c, int device, uint32_t max_slices, 
     { u32 const l3 = (u32)prop.multiProcessorCount * KMP_KNOB("KMP_MATCH_WAVES_PER_CU_L3", 16); c->match_blocks_l3 = l3 < blocks ? l3 : blocks; c->l3_team_slots = l3 * teams_per_wave; }
     c->big = c->max_slice_bytes > KMP_MAX_SLICE_BYTES;
     u32 const block_cap = c->big ? KMP_MAX_SLICE_BYTES : c->max_slice_bytes;     // the sequence / literal workspaces hold one block
-    c->seq_cap = (block_cap / 4 + 8 + 15) & ~15u; c->lit_cap = block_cap + 64; c->scratch_words = block_cap / 4 + 64;
+    { KWorkCaps const w = kx_work_caps(block_cap); c->seq_cap = w.seq_cap; c->lit_cap = w.lit_cap; c->scratch_words = w.scratch_words; }
     size_t const ns = max_slices;
     if (c->big) {
         c->big_G = (int)KMP_KNOB("KMP_BIG_TEAM_LANES", 0);      // 0 = by batch size (zstd_compress_big)
@@ -498,7 +482,7 @@ static int batch_create_body(kmp_batch_ctx* c, int device, uint32_t max_slices, 
     KMP_TRY(c->len_ok.alloc(ns * sizeof(u32), "hipMalloc(slice lengths)"));
     KMP_TRY(c->d_status.alloc(64, "hipMalloc(status word)"));
     HIP_TRY(hipMemsetAsync(c->d_status, 0, 64, c->st2));
-    c->knob.chunks = KMP_KNOB("KMP_ZSTD_CHUNKS", 0); c->knob.match_flags = KMP_KNOB("KMP_MATCH_FLAGS", 6); c->knob.entropy_pad = KMP_KNOB("KMP_ENTROPY_PAD_LDS", 0);
+    c->knob.chunks = KMP_KNOB("KMP_ZSTD_CHUNKS", 0); c->knob.match_flags = KMP_KNOB("KMP_MATCH_FLAGS", KXM_NT_STORES | KXM_NO_LITS); c->knob.entropy_pad = KMP_KNOB("KMP_ENTROPY_PAD_LDS", 0);
     c->knob.first_permille = KMP_KNOB("KMP_ZSTD_FIRST_PERMILLE", 500); c->knob.fast_first_permille = KMP_KNOB("KMP_ZSTD_FAST_FIRST_PERMILLE", 550); c->knob.entropy_flags = KMP_KNOB("KMP_ENTROPY_FLAGS", 0);
     c->knob.decode_flags = KMP_KNOB("KMP_DECODE_FLAGS", 0); c->knob.decode_pad = KMP_KNOB("KMP_DECODE_PAD_LDS", 0);
     c->knob.big_rounds = KMP_KNOB("KMP_BIG_ROUNDS", 0); c->knob.big_spw = KMP_KNOB("KMP_BIG_SLICES_PER_WAVE", 0);
@@ -633,11 +617,19 @@ extern "C" size_t kmp_zstd_compress_bound(size_t n)
 {
     return n + (n >> 8) + ((n < (128u << 10)) ? (((128u << 10) - n) >> 11) : 0);
 }
+// A batch as this context's compress kernels see it: the caller's arrays (the lengths: the sanitised copy) over the context's workspace.
+static KBatchView batch_view(kmp_batch_ctx* c, const void* d_src, const uint64_t* d_in_off, uint32_t n, void* d_dst, const uint64_t* d_out_off, uint32_t* d_out_len)
+{
+    KBatchView v = { (const u8*)d_src, d_in_off, c->len_ok, (u8*)d_dst, d_out_off, d_out_len, n, c->seqs, c->lits, c->meta, c->scratch,
+                     kx_work_caps(c->big ? KMP_MAX_SLICE_BYTES : c->max_slice_bytes) };
+    return v;
+}
+static KTeamTables team_tables(kmp_batch_ctx* c) { KTeamTables t = { c->tables, c->team_epoch, c->tseg, c->tseg_n, false }; return t; }
 // the tables of the one-position-per-step parsers (levels 1 / 2, dictionary): the level-3 tables when those are one piece,
 // else a piece of their own with its own epochs (measured over the spread tables: level 1 19.8 GB/s against 23.9)
-static int flat_tables(kmp_batch_ctx* c, u32** tables, u32** epochs)
+static int flat_tables(kmp_batch_ctx* c, KTeamTables* t)
 {
-    if (c->tseg_n == 1) { *tables = c->tables; *epochs = c->team_epoch; return KMP_OK; }
+    if (c->tseg_n == 1) { *t = kx_one_piece(c->tables, c->team_epoch); return KMP_OK; }
     auto fill = [c](table_part& f) {
         size_t const tbytes = (size_t)c->nteams * KX_TBL_ENTRIES * sizeof(u32);
         KMP_TRY(place_alloc(f.tables, tbytes, nullptr, nullptr));
@@ -647,7 +639,7 @@ static int flat_tables(kmp_batch_ctx* c, u32** tables, u32** epochs)
         return KMP_OK;
     };
     if (!c->flat) KMP_TRY(build_part(c->flat, KMP_PART_FLAT_TABLES, fill));
-    *tables = c->flat->tables; *epochs = c->flat->epochs;
+    *t = kx_one_piece(c->flat->tables, c->flat->epochs);
     return KMP_OK;
 }
 
@@ -658,25 +650,20 @@ static int zstd_compress_dfast(kmp_batch_ctx* c, const void* d_src, const uint64
 // The batch goes through in pieces that share one workspace (20 bytes a position: the sorted positions with their first bytes, where each
 // position stands): sort, then the wave-per-slice parse; the entropy kernel runs once over the whole batch.
 static int lazy_workspace(kmp_batch_ctx* c, u32 need_bytes);
-static int lazy_parse(kmp_batch_ctx* c, hipStream_t st, const void* d_src, const uint64_t* d_in_off, u32 n, u32 first0, int level);
+static int lazy_parse(kmp_batch_ctx* c, hipStream_t st, KBatchView const& v, int level);
 static int zstd_compress_lazy(kmp_batch_ctx* c, const void* d_src, const uint64_t* d_in_off, const uint32_t* d_in_len,
                               uint32_t n, void* d_dst, const uint64_t* d_out_off, uint32_t* d_out_len, void* hip_stream, int level)
 {
-    if (!c || (n && (!d_src || !d_in_off || !d_in_len || !d_dst || !d_out_off || !d_out_len))) { g_last_error = "kmp_zstd_compress_batch_level: null argument"; return KMP_ERR_ARG; }
-    if (n > c->max_slices) { g_last_error = "kmp_zstd_compress_batch_level: n exceeds the context's max_slices"; return KMP_ERR_CAPACITY; }
+    KMP_TRY(batch_args("kmp_zstd_compress_batch_level", c, n, { d_src, d_in_off, d_in_len, d_dst, d_out_off, d_out_len }));
     if (c->big) { g_last_error = "kmp_zstd_compress_batch_level: levels 5 .. 10 are served for slices up to 128 KiB"; return KMP_ERR_CAPACITY; }
     if (n == 0) return KMP_OK;
     hipStream_t const st = (hipStream_t)hip_stream;
     HIP_TRY(hipSetDevice(c->device));
     KMP_TRY(batch_begin(c, st, d_in_len, n, c->max_slice_bytes));          // (first: waits for the context's previous batch, whose workspace this may replace)
     KMP_TRY(lazy_workspace(c, c->max_slice_bytes));
-    KMP_TRY(lazy_parse(c, st, d_src, d_in_off, n, 0, level));
-    KEntropyArgs e;
-    e.src = (const u8*)d_src; e.in_off = d_in_off; e.in_len = c->len_ok; e.n_slices = n;
-    e.seqs = c->seqs; e.seq_cap = c->seq_cap; e.lits = c->lits; e.lit_cap = c->lit_cap; e.meta = c->meta;
-    e.scratch = c->scratch; e.scratch_words = c->scratch_words;
-    e.dst = (u8*)d_dst; e.out_off = d_out_off; e.out_len = d_out_len;
-    e.flags = 8u | ((u32)level << 12);           // literals are gathered by the entropy kernel; the level: it derives each slice's strategy from it
+    KBatchView const v = batch_view(c, d_src, d_in_off, n, d_dst, d_out_off, d_out_len);
+    KMP_TRY(lazy_parse(c, st, v, level));
+    KEntropyArgs const e = kx_entropy_args(v, kx_entropy_flags_lazy(level));      // literals are gathered by the entropy kernel; the level: it derives each slice's strategy from it
     hipLaunchKernelGGL(k_zstd_entropy, dim3(n), dim3(64), 0, st, e);
     HIP_TRY(hipGetLastError());
     c->last_chunks = 1; c->zstd_timed = 0;          // (no per-chunk timings: those are level 3's)
@@ -685,7 +672,7 @@ static int zstd_compress_lazy(kmp_batch_ctx* c, const void* d_src, const uint64_
 // need_bytes: the largest slice these kernels will parse (level 4 hands them only its slices up to 16 KiB: a quarter of the memory)
 static int lazy_workspace(kmp_batch_ctx* c, u32 need_bytes)
 {
-    u32 const pos_cap = (need_bytes + 63u) & ~63u;
+    u32 const pos_cap = kx_work_caps(need_bytes).pos_cap;
     if (c->lz && c->lz->pos_cap < pos_cap) c->lz.reset();                  // made for a smaller need: once more, larger
     if (c->lz) return KMP_OK;
     auto fill = [c, pos_cap](lazy_part& z) {
@@ -698,18 +685,15 @@ static int lazy_workspace(kmp_batch_ctx* c, u32 need_bytes)
     };
     return build_part(c->lz, KMP_PART_LAZY_LEVELS, fill);
 }
-// sort + parse of the slices [first0, first0 + n) of a batch, piece by piece (the slices' sanitised lengths are c->len_ok; sequences and
-// the per-slice record go where the other parsers put theirs).  Slices the level does not parse this way at their size are skipped: at
+// sort + parse of the slices of v (a batch or a chunk of one), piece by piece (sequences and the per-slice record go where the other
+// parsers put theirs).  Slices the level does not parse this way at their size are skipped: at
 // level 4 their record stays what k_zstd_match left (it serves 16 KiB < size <= 128 KiB), at the other levels it says "not served".
-static int lazy_parse(kmp_batch_ctx* c, hipStream_t st, const void* d_src, const uint64_t* d_in_off, u32 n, u32 first0, int level)
+static int lazy_parse(kmp_batch_ctx* c, hipStream_t st, KBatchView const& v, int level)
 {
     lazy_part const& z = *c->lz;
-    for (u32 first = first0; first < first0 + n; first += z.chunk) {
-        u32 const m = (first0 + n - first < z.chunk) ? first0 + n - first : z.chunk;
-        KLazyArgs g;
-        g.src = (const u8*)d_src; g.in_off = d_in_off + first; g.in_len = c->len_ok + first; g.n_slices = m;
-        g.rec = (KLazyRec*)z.srt.p; g.wr = z.wr; g.pos_cap = z.pos_cap;
-        g.seqs = c->seqs + (size_t)first * c->seq_cap; g.seq_cap = c->seq_cap; g.meta = c->meta + first; g.level = (u32)level;
+    for (u32 first = 0; first < v.n; first += z.chunk) {
+        u32 const m = (v.n - first < z.chunk) ? v.n - first : z.chunk;
+        KLazyArgs g = kx_lazy_args(v.sub(first, m), (KLazyRec*)z.srt.p, z.wr, z.pos_cap, level);
         // (the parse takes the costliest slices first: cost classes from the sort, a counting sort of the classes; batches worth ordering only)
         u32* const ord = (m >= 1024u && z.order) ? z.order.p : nullptr;
         if (ord) { g.order_key = ord; g.order_hist = ord + z.chunk; HIP_TRY(hipMemsetAsync(g.order_hist, 0, 256 * sizeof(u32), st)); }
@@ -730,15 +714,15 @@ extern "C" int kmp_zstd_compress_batch_level(kmp_batch_ctx* c, const void* d_src
     if (level >= 5 && level <= 10) return zstd_compress_lazy(c, d_src, d_in_off, d_in_len, n, d_dst, d_out_off, d_out_len, hip_stream, level);
     bool const neg = level < 0;                // negative levels: strategy "fast" with a step of 1 - level, literals left uncompressed
     if ((level != 1 && level != 2 && !neg) || level < -131072) { g_last_error = "kmp_zstd_compress_batch_level: levels -131072 .. -1 and 1 .. 10 are served"; return KMP_ERR_ARG; }
-    if (!c || (n && (!d_src || !d_in_off || !d_in_len || !d_dst || !d_out_off || !d_out_len))) { g_last_error = "kmp_zstd_compress_batch_level: null argument"; return KMP_ERR_ARG; }
-    if (n > c->max_slices) { g_last_error = "kmp_zstd_compress_batch_level: n exceeds the context's max_slices"; return KMP_ERR_CAPACITY; }
+    KMP_TRY(batch_args("kmp_zstd_compress_batch_level", c, n, { d_src, d_in_off, d_in_len, d_dst, d_out_off, d_out_len }));
     if (n == 0) return KMP_OK;
     hipStream_t const st = (hipStream_t)hip_stream;
     HIP_TRY(hipSetDevice(c->device));
     if (c->big) {
         // frames of several blocks, any size the context holds: beyond the level's window (512 KiB at level 1 and at the negative levels,
         // 1 MiB at level 2) libzstd's staging buffer wraps and the window slides (zstd_match_fast_ext_body)
-        return zstd_compress_big(c, d_src, d_in_off, d_in_len, n, d_dst, d_out_off, d_out_len, st, 0, neg ? 1u : (u32)level, 0, neg ? (u32)(1 - level) : 0u);
+        KBigLevel const b = kx_big_level(level);
+        return zstd_compress_big(c, d_src, d_in_off, d_in_len, n, d_dst, d_out_off, d_out_len, st, KXF_ONE_SHOT, b.strategy, 0, b.fast_step0, b.level4);
     }
     KMP_TRY(batch_begin(c, st, d_in_len, n, c->max_slice_bytes));
     HIP_TRY(hipMemsetAsync(c->counter, 0, 4 * KMP_MAX_CHUNKS, st));
@@ -751,23 +735,18 @@ extern "C" int kmp_zstd_compress_batch_level(kmp_batch_ctx* c, const void* d_src
     u32 starts[3] = { 0, n, n };
     if (chunks == 2) { u32 const pm = c->knob.fast_first_permille; starts[1] = (u32)((u64)n * (pm >= 100 && pm <= 950 ? pm : 500u) / 1000u) & ~63u; if (starts[1] == 0 || starts[1] >= n) chunks = 1, starts[1] = n; }
     bool forked = false;
+    KBatchView const v = batch_view(c, d_src, d_in_off, n, d_dst, d_out_off, d_out_len);
+    KTeamTables flat; KMP_TRY(flat_tables(c, &flat));
     for (u32 ci = 0; ci < chunks; ci++) {
         u32 const first = starts[ci], m_n = starts[ci + 1] - first;
         if (m_n == 0) continue;
-        KFastArgs g;
-        g.m.src = (const u8*)d_src; g.m.in_off = d_in_off + first; g.m.in_len = c->len_ok + first; g.m.n_slices = m_n;
-        g.m.seqs = c->seqs + (size_t)first * c->seq_cap; g.m.seq_cap = c->seq_cap; g.m.lits = c->lits + (size_t)first * c->lit_cap; g.m.lit_cap = c->lit_cap; g.m.meta = c->meta + first;
-        { u32* ft_ = nullptr; u32* fe_ = nullptr; KMP_TRY(flat_tables(c, &ft_, &fe_)); g.m.tables = ft_; g.m.tseg_n = 1; g.m.team_epoch = fe_; } g.m.counter = c->counter + ci; g.m.flags = 6; g.m.fstate = nullptr; g.m.big_tables = nullptr;
-        g.level = neg ? 0u : (u32)level; g.step0 = neg ? (u32)(1 - level) : 2u;
+        KBatchView const cv = v.sub(first, m_n);
+        KFastArgs const g = kx_fast_args(cv, flat, c->counter + ci, level);
         u32 blocks = (m_n + tpw - 1) / tpw; if (blocks > c->match_blocks) blocks = c->match_blocks;
         by_team_width(c->G, [&](auto w) { hipLaunchKernelGGL(k_zstd_match_fast<decltype(w)::value>, dim3(blocks), dim3(64), 0, st, g); });
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipEventRecord(c->match[ci].end, st));
-        KEntropyArgs e;
-        e.src = (const u8*)d_src; e.in_off = d_in_off + first; e.in_len = c->len_ok + first; e.n_slices = m_n;
-        e.seqs = g.m.seqs; e.seq_cap = c->seq_cap; e.lits = g.m.lits; e.lit_cap = c->lit_cap; e.meta = g.m.meta;
-        e.scratch = c->scratch + (size_t)first * c->scratch_words; e.scratch_words = c->scratch_words;
-        e.dst = (u8*)d_dst; e.out_off = d_out_off + first; e.out_len = d_out_len + first; e.flags = 8u | 32u | (neg ? 64u : 0u);   // gather literals; strategy "fast"; negative levels: literals stay raw
+        KEntropyArgs const e = kx_entropy_args(cv, kx_entropy_flags_fast(neg));   // gather literals; strategy "fast"; negative levels: literals stay raw
         hipStream_t es = st;
         if (ci + 1 < chunks) { es = c->st2; HIP_TRY(hipStreamWaitEvent(es, c->match[ci].end, 0)); forked = true; }
         hipLaunchKernelGGL(k_zstd_entropy, dim3(m_n), dim3(64), 0, es, e);
@@ -791,8 +770,7 @@ extern "C" int kmp_zstd_compress_batch_dict(kmp_batch_ctx* c, const void* d_src,
                                             uint32_t n, void* d_dst, const uint64_t* d_out_off, uint32_t* d_out_len,
                                             const void* h_dict, uint32_t dict_size, void* hip_stream)
 {
-    if (!c || !h_dict || (n && (!d_src || !d_in_off || !d_in_len || !d_dst || !d_out_off || !d_out_len))) { g_last_error = "kmp_zstd_compress_batch_dict: null argument"; return KMP_ERR_ARG; }
-    if (n > c->max_slices) { g_last_error = "kmp_zstd_compress_batch_dict: n exceeds the context's max_slices"; return KMP_ERR_CAPACITY; }
+    KMP_TRY(batch_args("kmp_zstd_compress_batch_dict", c, n, { d_src, d_in_off, d_in_len, d_dst, d_out_off, d_out_len }, h_dict != nullptr));
     if (c->big) { g_last_error = "kmp_zstd_compress_batch_dict: slices above 128 KiB are not served with a dictionary"; return KMP_ERR_CAPACITY; }
     if (dict_size < 8 || dict_size > KX_MAX_DICT) { g_last_error = "kmp_zstd_compress_batch_dict: dictionary of 8 .. 130560 bytes expected"; return KMP_ERR_CAPACITY; }
     if (n == 0) return KMP_OK;
@@ -832,22 +810,14 @@ extern "C" int kmp_zstd_compress_batch_dict(kmp_batch_ctx* c, const void* d_src,
     dict_part const& dp = *c->dict;
     KMP_TRY(batch_begin(c, st, d_in_len, n, c->max_slice_bytes));
     HIP_TRY(hipMemsetAsync(c->counter, 0, 4, st));
-    KDictArgs g;
-    g.m.src = (const u8*)d_src; g.m.in_off = d_in_off; g.m.in_len = c->len_ok; g.m.n_slices = n;
-    g.m.seqs = c->seqs; g.m.seq_cap = c->seq_cap; g.m.lits = c->lits; g.m.lit_cap = c->lit_cap; g.m.meta = c->meta;
-    { u32* ft_ = nullptr; u32* fe_ = nullptr; KMP_TRY(flat_tables(c, &ft_, &fe_)); g.m.tables = ft_; g.m.tseg_n = 1; g.m.team_epoch = fe_; } g.m.counter = c->counter; g.m.flags = 6; g.m.fstate = nullptr; g.m.big_tables = nullptr;
-    g.dict = dp.content; g.dict_size = dp.content_size; g.dictL = dp.L; g.dictS = dp.S; g.rep0 = dp.rep[0]; g.rep1 = dp.rep[1];
-    g.dWindowLog = dp.W; g.dHashLog = dp.H; g.dChainLog = dp.C; g.dMinMatch = dp.M;
+    KBatchView const v = batch_view(c, d_src, d_in_off, n, d_dst, d_out_off, d_out_len);
+    KTeamTables flat; KMP_TRY(flat_tables(c, &flat));
+    KDictArgs const g = kx_dict_args(v, flat, c->counter, dp.content, dp.content_size, dp.L, dp.S, dp.W, dp.H, dp.C, dp.M, dp.rep[0], dp.rep[1]);
     u32 const tpw = 64 / (u32)c->G;
     u32 blocks = (n + tpw - 1) / tpw; if (blocks > c->match_blocks) blocks = c->match_blocks;
     by_team_width(c->G, [&](auto w) { hipLaunchKernelGGL(k_zstd_match_dict<decltype(w)::value>, dim3(blocks), dim3(64), 0, st, g); });
     HIP_TRY(hipGetLastError());
-    KEntropyArgs e;
-    e.src = (const u8*)d_src; e.in_off = d_in_off; e.in_len = c->len_ok; e.n_slices = n;
-    e.seqs = c->seqs; e.seq_cap = c->seq_cap; e.lits = c->lits; e.lit_cap = c->lit_cap; e.meta = c->meta;
-    e.scratch = c->scratch; e.scratch_words = c->scratch_words;
-    e.dst = (u8*)d_dst; e.out_off = d_out_off; e.out_len = d_out_len; e.flags = 8u;       // literals are gathered by the entropy kernel
-    e.prior = dp.prior;
+    KEntropyArgs const e = kx_entropy_args(v, KXE_GATHER_LITS, dp.prior);       // literals are gathered by the entropy kernel
     if (dp.prior) hipLaunchKernelGGL(k_zstd_entropy_prior, dim3(n), dim3(64), 0, st, e);
     else hipLaunchKernelGGL(k_zstd_entropy, dim3(n), dim3(64), 0, st, e);
     HIP_TRY(hipGetLastError());
@@ -862,10 +832,8 @@ extern "C" int kmp_zstd_compress_batch_dict(kmp_batch_ctx* c, const void* d_src,
 int zstd_compress_big(kmp_batch_ctx* c, const void* d_src, const uint64_t* d_in_off, const uint32_t* d_in_len,
                       uint32_t n, void* d_dst, const uint64_t* d_out_off, uint32_t* d_out_len, hipStream_t st, u32 stream, u32 strategy, u32 tail_direct, u32 fast_step0, bool level4)
 {
-    bool const streaming = stream == 1 || stream == 2;
-    const uint32_t* const d_in_len_caller = d_in_len;
+    bool const streaming = stream == KXF_STREAM || stream == KXF_STREAM_EMPTY_END;
     KMP_TRY(batch_begin(c, st, d_in_len, n, c->max_slice_bytes));
-    d_in_len = c->len_ok;
     if (level4) {
         // level 4's double-fast rows on this path (16 - 128 KiB: hash 17 / chain 17; above 256 KiB and streams: 18 / 18): per-slice tables of
         // 2 MiB, allocated by the first such batch of the context
@@ -876,32 +844,19 @@ int zstd_compress_big(kmp_batch_ctx* c, const void* d_src, const uint64_t* d_in_
     HIP_TRY(hipMemsetAsync(c->big_tables, 0, (size_t)n * KX_BIG_TBL_ENTRIES * sizeof(u32), st));
     HIP_TRY(hipMemsetAsync(c->remaining, 0, 4, st));
     // strategy: 0 level 3 (double-fast), 1 level 1 (fast), 2 level 2 (fast, but double-fast for 128 KiB < size <= 256 KiB when the size is known)
-    u32 const level2 = strategy == 2u ? 1u : 0u;
-    hipLaunchKernelGGL(k_zstd_frame_init, dim3((n + 255) / 256), dim3(256), 0, st, d_in_len, n, c->fstate, (u8*)d_dst, d_out_off, d_out_len, c->remaining, streaming ? (strategy == 1u ? 0x48u : strategy == 2u ? 0x50u : 0x58u) : 0u, stream != 0 ? 1u : 0u, level4 ? 1u : 0u, c->d_status);
+    KBatchView const v = batch_view(c, d_src, d_in_off, n, d_dst, d_out_off, d_out_len);
+    hipLaunchKernelGGL(k_zstd_frame_init, dim3((n + 255) / 256), dim3(256), 0, st, v.in_len, n, c->fstate, v.dst, d_out_off, d_out_len, c->remaining, kx_big_window_byte(stream, strategy), stream != KXF_ONE_SHOT ? 1u : 0u, level4 ? 1u : 0u, c->d_status);
     HIP_TRY(hipGetLastError());
-    KMatchArgs m;
-    m.src = (const u8*)d_src; m.in_off = d_in_off; m.in_len = d_in_len; m.n_slices = n;
-    m.seqs = c->seqs; m.seq_cap = c->seq_cap; m.meta = c->meta; m.lits = c->lits; m.lit_cap = c->lit_cap;
-    m.tables = c->tables; for (int ts_ = 0; ts_ < 4; ts_++) m.tseg[ts_] = c->tseg[ts_]; m.tseg_n = c->tseg_n; m.team_epoch = c->team_epoch; m.counter = c->counter;
-    m.flags = 2u | (streaming ? 8u : 0u) | (c->max_slice_bytes >= KX_BLK_WIDE_FROM ? 16u : 0u);
-    m.fstate = c->fstate; m.big_tables = c->big_tables;
-    if (level4) { m.level = 4; m.big_tables = c->chain_t4->tables; m.big_stride = KX_BIG4_ENTRIES; m.big_long = KX_BIG4_LONG; }
-    KFrameArgs e;
-    e.src = (const u8*)d_src; e.in_off = d_in_off; e.in_len = d_in_len; e.n_slices = n;
-    e.seqs = c->seqs; e.seq_cap = c->seq_cap; e.lits = c->lits; e.lit_cap = c->lit_cap; e.meta = c->meta;
-    e.scratch = c->scratch; e.scratch_words = c->scratch_words;
-    e.dst = (u8*)d_dst; e.out_off = d_out_off; e.out_len = d_out_len;
-    e.fstate = c->fstate; e.hufct = c->hufct; e.remaining = c->remaining; e.stream = stream; e.strategy = strategy ? 1u : 0u; e.level2 = level2; e.cls = 0;
-    e.fast_step0 = strategy == 1u ? fast_step0 : 0u;         // a negative level: the level-1 machinery (window 2^19) on row 0 of the tables, a step of 1 - level, raw literals
-    e.tail_direct = stream == 3 ? 0u : tail_direct; e.out_chunk = stream == 3 ? tail_direct : 0u;      // (one parameter: the mode says which it is)
-    e.status_word = c->d_status;
+    KMatchArgs const m = kx_match_args_blk(v, team_tables(c), c->counter, streaming, c->max_slice_bytes >= KX_BLK_WIDE_FROM, c->fstate, level4 ? c->chain_t4->tables.p : c->big_tables.p, level4);
+    // (a negative level: the level-1 machinery (window 2^19) on row 0 of the tables, a step of 1 - level, raw literals)
+    KBigLevel const lv = { strategy, fast_step0, level4 };
+    KFrameArgs const e = kx_frame_args(v, c->fstate, c->hufct, c->remaining, c->d_status, stream, lv, tail_direct);
 #ifdef KMP_ABLATIONS
     if (strategy || c->knob.big_rounds == 0)
 #endif
     {
         // one wave per slice walks its chain of blocks
         // few slices: one per wave (most waves); many: up to 64 / G per wave so that all of them are in flight
-        KBigArgs g; g.m = m; g.e = e; g.counters = c->big_counters;
         // lanes per slice: every slice of the batch should be in flight (its block chain is serial), and a parse team
         // gains little beyond 8 lanes -- measured on 1 MiB and 256 KiB slices: 8 lanes up to 16 K slices, 4 above
         int const bigG = c->big_G ? c->big_G : (n >= 16384u ? 4 : 8);
@@ -913,22 +868,22 @@ int zstd_compress_big(kmp_batch_ctx* c, const void* d_src, const uint64_t* d_in_
             // long as its fullest CU (8 192 x 1 MiB: 3 slices per wave = 2 731 waves 6.5 GB/s, 4 = 2 048 waves 7.3)
             for (u32 t = spw; t <= 64u / (u32)bigG && t <= spw + 2u; t++) if (((n + t - 1) / t) % c->cus == 0) { spw = t; break; }
         }
-        g.spw = spw;
+        KBigArgs g = kx_big_args(m, e, c->big_counters, spw);
         u32 const grid = (n + spw - 1) / spw;
         HIP_TRY(hipMemsetAsync(c->big_counters, 0, (size_t)n * 4, st));
-        if (level2 && !streaming) {
+        if (strategy == 2u && !streaming) {
             // level 2, sizes known: the slices of its double-fast row first (class 1), the others (class 2) through the fast parser below
-            g.e.strategy = 0; g.e.cls = 1; g.m.flags = m.flags | 32u | (1u << 6);
+            kx_big_set_class(g, m.flags, KXC_L2_DFAST);
             by_team_width(bigG, [&](auto w) { hipLaunchKernelGGL(k_zstd_big<decltype(w)::value>, dim3(grid), dim3(64), 0, st, g); });
             HIP_TRY(hipGetLastError());
             HIP_TRY(hipMemsetAsync(c->big_counters, 0, (size_t)n * 4, st));
-            g.e.strategy = 1; g.e.cls = 2; g.m.flags = m.flags | (2u << 6);
+            kx_big_set_class(g, m.flags, KXC_L2_FAST);
         }
         if (strategy) by_team_width(bigG, [&](auto w) { hipLaunchKernelGGL(k_zstd_big_fast<decltype(w)::value>, dim3(grid), dim3(64), 0, st, g); });
         else by_team_width(bigG, [&](auto w) { hipLaunchKernelGGL(k_zstd_big<decltype(w)::value>, dim3(grid), dim3(64), 0, st, g); });
         HIP_TRY(hipGetLastError());
         c->last_rounds = 0; c->last_chunks = 1; c->zstd_timed = 0;
-        return batch_end(c, st, d_in_len_caller, n, c->max_slice_bytes, d_out_len, nullptr);
+        return batch_end(c, st, d_in_len, n, c->max_slice_bytes, d_out_len, nullptr);
     }
 #ifdef KMP_ABLATIONS
     // (experiment switch KMP_BIG_ROUNDS=1) the same steps as separate launches per round of blocks
@@ -949,7 +904,7 @@ int zstd_compress_big(kmp_batch_ctx* c, const void* d_src, const uint64_t* d_in_
         HIP_TRY(hipGetLastError());
     }
     c->last_rounds = rounds; c->last_chunks = 1; c->zstd_timed = 0;
-    return batch_end(c, st, d_in_len_caller, n, c->max_slice_bytes, d_out_len, nullptr);
+    return batch_end(c, st, d_in_len, n, c->max_slice_bytes, d_out_len, nullptr);
 #else
     g_last_error = "zstd_compress_big: unreachable"; return KMP_ERR_ARG;
 #endif
@@ -969,12 +924,13 @@ extern "C" int kmp_zstd_compress_batch_stream_level(kmp_batch_ctx* c, const void
     if (level == 0) level = 3;
     bool const neg = level < 0;
     if ((level < 1 && !neg) || level > 4 || level < -131072) { g_last_error = "kmp_zstd_compress_batch_stream_level: levels -131072 .. -1 and 1 .. 4 are served"; return KMP_ERR_ARG; }
-    if (!c || (n && (!d_src || !d_in_off || !d_in_len || !d_dst || !d_out_off || !d_out_len))) { g_last_error = "kmp_zstd_compress_batch_stream: null argument"; return KMP_ERR_ARG; }
+    KMP_TRY(args_present("kmp_zstd_compress_batch_stream", c != nullptr, n, { d_src, d_in_off, d_in_len, d_dst, d_out_off, d_out_len }));
     if (!c->big) { g_last_error = "kmp_zstd_compress_batch_stream: the context must be created with max_slice_bytes above 128 KiB"; return KMP_ERR_CAPACITY; }
-    if (n > c->max_slices) { g_last_error = "kmp_zstd_compress_batch_stream: n exceeds the context's max_slices"; return KMP_ERR_CAPACITY; }
+    KMP_TRY(args_count("kmp_zstd_compress_batch_stream", c, n));
     if (n == 0) return KMP_OK;
     HIP_TRY(hipSetDevice(c->device));
-    return zstd_compress_big(c, d_src, d_in_off, d_in_len, n, d_dst, d_out_off, d_out_len, (hipStream_t)hip_stream, empty_end ? 2u : 1u, (level == 3 || level == 4) ? 0u : neg ? 1u : (u32)level, 0, neg ? (u32)(1 - level) : 0u, level == 4);
+    KBigLevel const b = kx_big_level(level);
+    return zstd_compress_big(c, d_src, d_in_off, d_in_len, n, d_dst, d_out_off, d_out_len, (hipStream_t)hip_stream, empty_end ? KXF_STREAM_EMPTY_END : KXF_STREAM, b.strategy, 0, b.fast_step0, b.level4);
 }
 /* What ZstdCompressor(level).transform(ByteArray) returns: above 128 KiB libzstd stages the input in chunks of 128 KiB
  * because the reference's output slices are smaller than ZSTD_compressBound (include/kompressor_hip.h). */
@@ -982,15 +938,15 @@ extern "C" int kmp_zstd_compress_batch_reference(kmp_batch_ctx* c, const void* d
                                                  uint32_t n, void* d_dst, const uint64_t* d_out_off, uint32_t* d_out_len, int level, uint32_t out_chunk, void* hip_stream)
 {
     if (level == 0) level = 3;
-    if (!c) { g_last_error = "kmp_zstd_compress_batch_reference: null argument"; return KMP_ERR_ARG; }
+    KMP_TRY(args_present("kmp_zstd_compress_batch_reference", c != nullptr, 0, {}));
     if (!c->big) return kmp_zstd_compress_batch_level(c, d_src, d_in_off, d_in_len, n, d_dst, d_out_off, d_out_len, level, hip_stream);   // one block: one chunk
     bool const neg = level < 0;
     if ((level < 1 && !neg) || level > 4 || level < -131072) { g_last_error = "kmp_zstd_compress_batch_reference: levels -131072 .. -1 and 1 .. 4 are served"; return KMP_ERR_ARG; }
-    if (n && (!d_src || !d_in_off || !d_in_len || !d_dst || !d_out_off || !d_out_len)) { g_last_error = "kmp_zstd_compress_batch_reference: null argument"; return KMP_ERR_ARG; }
-    if (n > c->max_slices) { g_last_error = "kmp_zstd_compress_batch_reference: n exceeds the context's max_slices"; return KMP_ERR_CAPACITY; }
+    KMP_TRY(batch_args("kmp_zstd_compress_batch_reference", c, n, { d_src, d_in_off, d_in_len, d_dst, d_out_off, d_out_len }));
     if (n == 0) return KMP_OK;
     HIP_TRY(hipSetDevice(c->device));
-    return zstd_compress_big(c, d_src, d_in_off, d_in_len, n, d_dst, d_out_off, d_out_len, (hipStream_t)hip_stream, 3u, (level == 3 || level == 4) ? 0u : neg ? 1u : (u32)level, out_chunk, neg ? (u32)(1 - level) : 0u, level == 4);
+    KBigLevel const b = kx_big_level(level);
+    return zstd_compress_big(c, d_src, d_in_off, d_in_len, n, d_dst, d_out_off, d_out_len, (hipStream_t)hip_stream, KXF_REFERENCE, b.strategy, out_chunk, b.fast_step0, b.level4);
 }
 /* block rounds of the last batch of a context for slices above 128 KiB */
 extern "C" int kmp_batch_last_rounds(kmp_batch_ctx* c) { return c ? (int)c->last_rounds : 0; }
@@ -1022,14 +978,13 @@ static int ensure_tables4(kmp_batch_ctx* c)
 static int zstd_compress_dfast(kmp_batch_ctx* c, const void* d_src, const uint64_t* d_in_off, const uint32_t* d_in_len,
                                uint32_t n, void* d_dst, const uint64_t* d_out_off, uint32_t* d_out_len, void* hip_stream, int level)
 {
-    if (!c || (n && (!d_src || !d_in_off || !d_in_len || !d_dst || !d_out_off || !d_out_len))) { g_last_error = "kmp_zstd_compress_batch: null argument"; return KMP_ERR_ARG; }
-    if (n > c->max_slices) { g_last_error = "kmp_zstd_compress_batch: n exceeds the context's max_slices"; return KMP_ERR_CAPACITY; }
+    KMP_TRY(batch_args("kmp_zstd_compress_batch", c, n, { d_src, d_in_off, d_in_len, d_dst, d_out_off, d_out_len }));
     if (n == 0) return KMP_OK;
     hipStream_t const st = (hipStream_t)hip_stream;
     HIP_TRY(hipSetDevice(c->device));
     bool const l4 = level == 4;
     if (l4 && !c->big) KMP_TRY(ensure_tables4(c));
-    if (c->big) return zstd_compress_big(c, d_src, d_in_off, d_in_len, n, d_dst, d_out_off, d_out_len, st, 0, 0, 0, 0, l4);
+    if (c->big) return zstd_compress_big(c, d_src, d_in_off, d_in_len, n, d_dst, d_out_off, d_out_len, st, KXF_ONE_SHOT, 0, 0, 0, l4);
     // Chunks: the match kernel of chunk i+1 (memory-transaction bound) runs beside the entropy kernel of
     // chunk i (latency bound) on a second stream; the caller's stream sees everything finished.
     // (two chunks only when each still fills at least half of the match kernel's team slots: 65 536 x 64 KiB -> 2,
@@ -1067,35 +1022,27 @@ static int zstd_compress_dfast(kmp_batch_ctx* c, const void* d_src, const uint64
     // two chunks: the last entropy launch is the only one nothing runs beside, so the second chunk is the smaller one
     if (chunks == 2) { u32 const pm = c->knob.first_permille; if (pm >= 100 && pm <= 950) starts[1] = (u32)((u64)n * pm / 1000u) & ~63u; if (starts[1] == 0 || starts[1] >= n) starts[1] = per; }
     bool forked = false;
+    KBatchView const v = batch_view(c, d_src, d_in_off, n, d_dst, d_out_off, d_out_len);
+    KTeamTables const tables = l4 ? kx_one_piece(c->t4->tables, c->t4->epochs, true) : team_tables(c);
     for (u32 ci = 0; ci < chunks; ci++) {
         u32 const first = starts[ci], m_n = starts[ci + 1] - first;
         if (m_n == 0) continue;
-        KMatchArgs m;
-        m.src = (const u8*)d_src; m.in_off = d_in_off + first; m.in_len = c->len_ok + first; m.n_slices = m_n;
-        m.seqs = c->seqs + (size_t)first * c->seq_cap; m.seq_cap = c->seq_cap; m.meta = c->meta + first;
-        m.lits = c->lits + (size_t)first * c->lit_cap; m.lit_cap = c->lit_cap;
-        m.tables = c->tables; for (int ts_ = 0; ts_ < 4; ts_++) m.tseg[ts_] = c->tseg[ts_]; m.tseg_n = c->tseg_n; m.team_epoch = c->team_epoch; m.counter = c->counter + ci; m.flags = match_flags;
+        KBatchView const cv = v.sub(first, m_n);
+        KMatchArgs m = kx_match_args(cv, tables, c->counter + ci, match_flags);
         u32 max_blocks = (u32)((u64)c->match_blocks_l3 * (64u / (u32)c->G) / tpw);      // the context's team slots at this batch's width
-        if (l4) {
-            m.tables = c->t4->tables; m.tseg_n = 1; m.team_epoch = c->t4->epochs; m.tbl_stride = KX_TBL4_ENTRIES; m.tbl_long = KX_TBL4_LONG; m.level = 4;
-            if (max_blocks > c->t4->teams / tpw) max_blocks = c->t4->teams / tpw;
-        }
+        if (l4 && max_blocks > c->t4->teams / tpw) max_blocks = c->t4->teams / tpw;
         u32 blocks = (m_n + tpw - 1) / tpw; if (blocks > max_blocks) blocks = max_blocks;
         if (c->profiling) HIP_TRY(hipEventRecord(c->match[ci].start, st));
-        KEntropyArgs e;
-        e.src = (const u8*)d_src; e.in_off = d_in_off + first; e.in_len = c->len_ok + first; e.n_slices = m_n;
-        e.seqs = m.seqs; e.seq_cap = c->seq_cap; e.lits = c->lits + (size_t)first * c->lit_cap; e.lit_cap = c->lit_cap; e.meta = m.meta;
-        e.scratch = c->scratch + (size_t)first * c->scratch_words; e.scratch_words = c->scratch_words;
-        e.dst = (u8*)d_dst; e.out_off = d_out_off + first; e.out_len = d_out_len + first; e.flags = c->knob.entropy_flags | ((m.flags & 4u) ? 8u : 0u);
 #ifdef KMP_ABLATIONS
         // the ablation build's other two forms of the level-3 step: the split-phase parser, the fused kernel
         bool const fuse = c->knob.fuse && !c->knob.match_v2 && !l4 && (G == 4 || G == 8);
         if (fuse) {
+            KEntropyArgs const e = kx_entropy_args(cv, c->knob.entropy_flags | kx_entropy_flags_dfast(m.flags, false));
             if (G == 4) hipLaunchKernelGGL(k_zstd_l3_fused<4>, dim3(blocks), dim3(64), 0, st, m, e);
             else hipLaunchKernelGGL(k_zstd_l3_fused<8>, dim3(blocks), dim3(64), 0, st, m, e);
         } else
         if (c->knob.match_v2 && !l4 && (G == 2 || G == 4 || G == 8)) {
-            m.flags |= 4u;                                                // this parser never copies literals: the entropy kernel gathers them
+            m.flags |= KXM_NO_LITS;                                       // this parser never copies literals: the entropy kernel gathers them
             bool const r512 = c->knob.match_v2 == 2;
             switch (G) {
             case 2:  hipLaunchKernelGGL((k_zstd_match2<2, 256>), dim3(blocks), dim3(64), 0, st, m); break;
@@ -1112,10 +1059,10 @@ static int zstd_compress_dfast(kmp_batch_ctx* c, const void* d_src, const uint64
             // level 4 up to 16 KiB is strategy "greedy" (ZSTD_getCParams(4, n <= 16 KiB)): those slices, which k_zstd_match has passed over, are
             // parsed by the kernels of levels 5 .. 10 (zstd_lazy.h), which pass over all the others
             KMP_TRY(lazy_workspace(c, c->max_slice_bytes < 16384u ? c->max_slice_bytes : 16384u));
-            KMP_TRY(lazy_parse(c, st, d_src, d_in_off, m_n, first, 4));
+            KMP_TRY(lazy_parse(c, st, cv, 4));
         }
         HIP_TRY(hipEventRecord(c->match[ci].end, st));
-        e.flags = c->knob.entropy_flags | ((m.flags & 4u) ? 8u : 0u) | (l4 ? (4u << 12) : 0u);
+        KEntropyArgs const e = kx_entropy_args(cv, c->knob.entropy_flags | kx_entropy_flags_dfast(m.flags, l4));
         hipStream_t es = st;
         if (ci + 1 < chunks) { es = c->st2; HIP_TRY(hipStreamWaitEvent(es, c->match[ci].end, 0)); forked = true; }
         if (c->profiling) HIP_TRY(hipEventRecord(c->entropy[ci].start, es));
@@ -1147,7 +1094,7 @@ extern "C" void kmp_batch_piece_range(uint32_t n, uint32_t pieces, uint32_t piec
 // the three steps of a batch in pieces (kmp_coalesce.h queues a piece as soon as its copy in is queued)
 int pieces_begin(kmp_batch_ctx* c, u32 pieces, void* const* hip_streams)
 {
-    if (!c || !hip_streams) { g_last_error = "kmp_zstd_compress_batch_pieces: null argument"; return KMP_ERR_ARG; }
+    KMP_TRY(args_present("kmp_zstd_compress_batch_pieces", c && hip_streams, 0, {}));
     if (pieces < 1 || pieces > KMP_MAX_PIECES) { g_last_error = "kmp_zstd_compress_batch_pieces: 1 .. 8 pieces"; return KMP_ERR_ARG; }
     if (c->big) { g_last_error = "kmp_zstd_compress_batch_pieces: contexts for slices up to 128 KiB only"; return KMP_ERR_CAPACITY; }
     if (c->match_blocks_l3 / pieces == 0) { g_last_error = "kmp_zstd_compress_batch_pieces: more pieces than the context has workgroups"; return KMP_ERR_ARG; }
@@ -1165,20 +1112,12 @@ int piece_enqueue(kmp_batch_ctx* c, u32 p, u32 pieces, const void* d_src, const 
     if (m_n == 0) { HIP_TRY(hipEventRecord(c->ev_piece[p], st)); return KMP_OK; }
     hipLaunchKernelGGL(k_len_guard, dim3((m_n + 255) / 256), dim3(256), 0, st, d_in_len + first, m_n, c->max_slice_bytes, c->len_ok + first, c->d_status);
     HIP_TRY(hipMemsetAsync(c->counter + p, 0, 4, st));
-    KMatchArgs m;
-    m.src = (const u8*)d_src; m.in_off = d_in_off + first; m.in_len = c->len_ok + first; m.n_slices = m_n;
-    m.seqs = c->seqs + (size_t)first * c->seq_cap; m.seq_cap = c->seq_cap; m.meta = c->meta + first;
-    m.lits = c->lits + (size_t)first * c->lit_cap; m.lit_cap = c->lit_cap;
-    m.tables = c->tables; for (int ts_ = 0; ts_ < 4; ts_++) m.tseg[ts_] = c->tseg[ts_]; m.tseg_n = c->tseg_n; m.team_epoch = c->team_epoch;
-    m.counter = c->counter + p; m.flags = c->knob.match_flags; m.block_base = p * blocks_per_piece;
+    KBatchView const v = batch_view(c, d_src, d_in_off, n, d_dst, d_out_off, d_out_len).sub(first, m_n);
+    KMatchArgs const m = kx_match_args(v, team_tables(c), c->counter + p, c->knob.match_flags, p * blocks_per_piece);
     u32 blocks = (m_n + tpw - 1) / tpw; if (blocks > blocks_per_piece) blocks = blocks_per_piece;
     by_team_width(c->G, [&](auto w) { hipLaunchKernelGGL(k_zstd_match<decltype(w)::value>, dim3(blocks), dim3(64), 0, st, m); });
     HIP_TRY(hipGetLastError());
-    KEntropyArgs e;
-    e.src = (const u8*)d_src; e.in_off = d_in_off + first; e.in_len = c->len_ok + first; e.n_slices = m_n;
-    e.seqs = m.seqs; e.seq_cap = c->seq_cap; e.lits = m.lits; e.lit_cap = c->lit_cap; e.meta = m.meta;
-    e.scratch = c->scratch + (size_t)first * c->scratch_words; e.scratch_words = c->scratch_words;
-    e.dst = (u8*)d_dst; e.out_off = d_out_off + first; e.out_len = d_out_len + first; e.flags = c->knob.entropy_flags | ((m.flags & 4u) ? 8u : 0u);
+    KEntropyArgs const e = kx_entropy_args(v, c->knob.entropy_flags | kx_entropy_flags_dfast(m.flags, false));
     hipLaunchKernelGGL(k_zstd_entropy, dim3(m_n), dim3(64), 0, st, e);
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(k_len_guard_finish, dim3((m_n + 255) / 256), dim3(256), 0, st, d_in_len + first, m_n, c->max_slice_bytes, d_out_len + first, c->meta + first, c->d_status);
@@ -1190,8 +1129,7 @@ int piece_enqueue(kmp_batch_ctx* c, u32 p, u32 pieces, const void* d_src, const 
 extern "C" int kmp_zstd_compress_batch_pieces(kmp_batch_ctx* c, const void* d_src, const uint64_t* d_in_off, const uint32_t* d_in_len, uint32_t n,
                                               void* d_dst, const uint64_t* d_out_off, uint32_t* d_out_len, uint32_t pieces, void* const* hip_streams)
 {
-    if (!c || !hip_streams || (n && (!d_src || !d_in_off || !d_in_len || !d_dst || !d_out_off || !d_out_len))) { g_last_error = "kmp_zstd_compress_batch_pieces: null argument"; return KMP_ERR_ARG; }
-    if (n > c->max_slices) { g_last_error = "kmp_zstd_compress_batch_pieces: n exceeds the context's max_slices"; return KMP_ERR_CAPACITY; }
+    KMP_TRY(batch_args("kmp_zstd_compress_batch_pieces", c, n, { d_src, d_in_off, d_in_len, d_dst, d_out_off, d_out_len }, hip_streams != nullptr));
     KMP_TRY(pieces_begin(c, pieces, hip_streams));
     if (n == 0) return KMP_OK;
     pieces_end end = { c, pieces, hip_streams, 0 };
@@ -1298,8 +1236,7 @@ static int zstd_decompress_impl(kmp_batch_ctx* c, const void* d_src, const uint6
                                 uint32_t n, void* d_dst, const uint64_t* d_out_off, const uint32_t* d_out_cap,
                                 uint32_t* d_out_len, uint32_t* d_status, const void* d_dict, uint32_t dict_size, void* hip_stream)
 {
-    if (!c || (n && (!d_src || !d_in_off || !d_in_len || !d_dst || !d_out_off || !d_out_cap || !d_out_len || !d_status))) { g_last_error = "kmp_zstd_decompress_batch: null argument"; return KMP_ERR_ARG; }
-    if (n > c->max_slices) { g_last_error = "kmp_zstd_decompress_batch: n exceeds the context's max_slices"; return KMP_ERR_CAPACITY; }
+    KMP_TRY(batch_args("kmp_zstd_decompress_batch", c, n, { d_src, d_in_off, d_in_len, d_dst, d_out_off, d_out_cap, d_out_len, d_status }));
     if (n == 0) return KMP_OK;
     hipStream_t const st = (hipStream_t)hip_stream;
     HIP_TRY(hipSetDevice(c->device));

@@ -89,7 +89,7 @@ int inflate_batch_impl(kmp_batch_ctx* c, const void* d_src, const uint64_t* d_in
                        int format, int window_bits, void* hip_stream)
 {
     if (format < 0 || format > 3 || window_bits < 0 || window_bits > 15) { g_last_error = "kmp_inflate_batch: format must be 0 (raw), 1 (zlib), 2 (gzip) or 3 (zlib or gzip)"; return KMP_ERR_ARG; }
-    if (!c || (n && (!d_src || !d_in_off || !d_in_len || !d_dst || !d_out_off || !d_out_cap || !d_out_len || !d_status))) { g_last_error = "kmp_inflate_batch: null argument"; return KMP_ERR_ARG; }
+    KMP_TRY(args_present("kmp_inflate_batch", c != nullptr, n, { d_src, d_in_off, d_in_len, d_dst, d_out_off, d_out_cap, d_out_len, d_status }));
     if (n == 0) return KMP_OK;
     hipStream_t const st = (hipStream_t)hip_stream;
     HIP_TRY(hipSetDevice(c->device));
@@ -149,8 +149,7 @@ int deflate_batch_impl(kmp_batch_ctx* c, const void* d_src, const uint64_t* d_in
                        uint32_t n, void* d_dst, const uint64_t* d_out_off, uint32_t* d_out_len, u32 format, void* hip_stream, int level,
                        int window_bits, int mem_level)
 {
-    if (!c || (n && (!d_src || !d_in_off || !d_in_len || !d_dst || !d_out_off || !d_out_len))) { g_last_error = "kmp_deflate_compress_batch: null argument"; return KMP_ERR_ARG; }
-    if (n > c->max_slices) { g_last_error = "kmp_deflate_compress_batch: n exceeds the context's max_slices"; return KMP_ERR_CAPACITY; }
+    KMP_TRY(batch_args("kmp_deflate_compress_batch", c, n, { d_src, d_in_off, d_in_len, d_dst, d_out_off, d_out_len }));
     if (n == 0) return KMP_OK;
     hipStream_t const st = (hipStream_t)hip_stream;
     HIP_TRY(hipSetDevice(c->device));

@@ -12,6 +12,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <initializer_list>
 #include <memory>
 #include <new>
 #include <string>
@@ -194,6 +195,26 @@ struct kmp_batch_ctx {
     struct { u32 chunks, match_flags, entropy_pad, first_permille, fast_first_permille, entropy_flags, decode_flags, decode_pad, big_rounds, big_spw,
                  dfl_chunk, dfl_chain_waves, dfl_serial, dfl_flags, decode_pre, decode_sort, decode_pieces, decode_stage_slices, inflate_pre, inflate_pieces, autotune, match_v2, fuse; } knob = {};
 };
+
+// The batch entry points' argument check.  fn: the name the message carries (an entry point may report for the one it serves).
+// args_present: a context and whatever else must be there even for an empty batch (ok), every array of a non-empty batch;
+// args_count: n against the context; batch_args: both.  The halves stand alone where an entry point has a check of its own between them.
+static inline int args_present(const char* fn, bool ok, u32 n, std::initializer_list<const void*> arrays)
+{
+    for (const void* p : arrays) if (n && !p) ok = false;
+    if (!ok) { g_last_error = std::string(fn) + ": null argument"; return KMP_ERR_ARG; }
+    return KMP_OK;
+}
+static inline int args_count(const char* fn, const kmp_batch_ctx* c, u32 n)
+{
+    if (n > c->max_slices) { g_last_error = std::string(fn) + ": n exceeds the context's max_slices"; return KMP_ERR_CAPACITY; }
+    return KMP_OK;
+}
+static inline int batch_args(const char* fn, const kmp_batch_ctx* c, u32 n, std::initializer_list<const void*> arrays, bool ok = true)
+{
+    KMP_TRY(args_present(fn, c && ok, n, arrays));
+    return args_count(fn, c, n);
+}
 
 // a context's owner (the host engines, the streaming contexts): kmp_batch_destroy on the context's device
 struct batch_deleter { void operator()(kmp_batch_ctx* c) const { kmp_batch_destroy(c); } };

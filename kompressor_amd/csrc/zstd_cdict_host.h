@@ -1,7 +1,7 @@
 // zstd_cdict_host.h -- host-side construction of libzstd's CDict for a raw-content dictionary at level 3:
 // parameters of ZSTD_getCParams(3, unknown source size, dictSize) in "create CDict" mode, then
 // ZSTD_fillDoubleHashTableForCDict over the dictionary (tagged entries: index << 8 | tag, index = position + 2).
-// Built once per dictionary on the host and uploaded (kmp_api.hip); the emulator harness uses the same code.
+// Built once per dictionary on the host and uploaded (kmp_batch.hip: kmp_zstd_compress_batch_dict); the emulator harness uses the same code.
 #pragma once
 #include <stdint.h>
 #include <string.h>

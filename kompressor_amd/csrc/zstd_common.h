@@ -130,7 +130,8 @@ KX_DEV KParams kx_params_l4(u32 n, bool& ok)
 // rows are "fast" ones (zstd_match_fast.h).  A batch at level 2 therefore goes through both block-chain kernels, each
 // taking the slices of its class (KFrameArgs.cls: 0 every slice, 1 only that size class, 2 only the others).
 KX_DEV KParams kx_params_l2_dfast() { KParams p; p.windowLog = 18; p.chainLog = 14; p.hashLog = 14; p.minMatch = 5; return p; }
-KX_DEV bool kx_in_class(u32 cls, u32 n) { return cls == 0u || ((n > 131072u && n <= 262144u) == (cls == 1u)); }
+enum : u32 { KXC_ALL = 0u, KXC_L2_DFAST = 1u, KXC_L2_FAST = 2u };
+KX_DEV bool kx_in_class(u32 cls, u32 n) { return cls == KXC_ALL || ((n > 131072u && n <= 262144u) == (cls == KXC_L2_DFAST)); }
 
 // What a formatted dictionary gives a DEcoder besides its content (libzstd: ZSTD_loadDEntropy): the literals' Huffman table as weights, the
 // three sequence tables as normalised counts -- the first block of a frame may refer to them as "the previous block's" (tree-less literals,

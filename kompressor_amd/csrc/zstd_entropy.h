@@ -27,9 +27,20 @@ struct KEntropyArgs {
     u32* scratch; u32 scratch_words;         // per slice: Huffman stream staging (u32 aligned)
     u8* dst; const u64* out_off; u32* out_len;
     const KDictPrior* prior = nullptr;       // k_zstd_entropy_prior only: the formatted dictionary's tables
-    u32 flags;                               // timing experiments only (results become wrong): 1 no literal coding, 2 no sequence coding (timing experiments, results become wrong);
-                                             // 8: the match kernel copied no literals, gather them here; 32: strategy "fast" (levels 1, 2); bits 8 .. 10: the strategy's number when it is another (3 greedy, 4 lazy, 5 lazy2);
-                                             // 64: literals are left uncompressed (negative levels: ZSTD_literalsCompressionIsDisabled)
+    u32 flags;                               // KXE_* below
+};
+// KEntropyArgs.flags (the low twelve bits travel on to kzstd_sequences as its xflags)
+enum : u32 {
+    KXE_NO_LIT_CODING  = 1u,                 // timing experiments only (results become wrong): no literal coding,
+    KXE_NO_SEQ_CODING  = 2u,                 //   no sequence coding,
+    KXE_TABLES_ONLY    = 16u,                //   the sequence tables are built, the bitstream is not written
+    KXE_GATHER_LITS    = 8u,                 // the parser copied no literals (KXM_NO_LITS; a parser that never does): gather them here
+    KXE_STRATEGY_FAST  = 32u,                // strategy "fast" (levels 1, 2 and the negative ones); without it and without a number: double-fast
+    KXE_RAW_LITS       = 64u,                // literals are left uncompressed (negative levels: ZSTD_literalsCompressionIsDisabled)
+    KXE_STRATEGY_SHIFT = 8u,                 // three bits: the strategy's number when it is another (3 greedy, 4 lazy, 5 lazy2).  No caller sets
+    KXE_STRATEGY_MASK  = 7u,                 //   them: the kernel writes them per slice from the level below and the slice's size
+    KXE_LEVEL_SHIFT    = 12u,                // from here up: the level (4 .. 10), or 0: every slice is of the strategy the bits above say
+    KXE_XFLAGS_MASK    = 0xFFFu,             // what kzstd_sequences gets
 };
 
 #define KXE_ERR 0xFFFFFFFFu
@@ -932,7 +943,7 @@ KX_DEV u32 kzstd_sequences(KEntropyLds& lds, u8* dst, const KSeq* seqs, u32 nbSe
         if (lane < 3) {
             u32 const lastCode = lane == 0 ? cl.ll : lane == 1 ? cl.of : cl.ml;
             u32 const firstCode = lane == 0 ? cf.ll : lane == 1 ? cf.of : cf.ml;
-            mySz = kx_build_seq_table(lds, lane, lds.hist + 64 * lane, nbSeq, lastCode, firstCode, myType, ct, (xflags >> 8) ? (xflags >> 8) & 7u : ((xflags & 32u) ? 1u : 2u), prior);
+            mySz = kx_build_seq_table(lds, lane, lds.hist + 64 * lane, nbSeq, lastCode, firstCode, myType, ct, (xflags >> KXE_STRATEGY_SHIFT) ? (xflags >> KXE_STRATEGY_SHIFT) & KXE_STRATEGY_MASK : ((xflags & KXE_STRATEGY_FAST) ? 1u : 2u), prior);
         }
     }
     kx_sync();
@@ -955,7 +966,7 @@ KX_DEV u32 kzstd_sequences(KEntropyLds& lds, u8* dst, const KSeq* seqs, u32 nbSe
     // tANS bitstream. Per 64-sequence chunk (walked last -> first): every lane stages one
     // sequence's codes; lanes 0..2 run the LL / OF / ML state chains; then every lane packs
     // its sequence's bits into an LDS buffer at a scanned bit offset; whole words go out.
-    if (xflags & 16u) return 0;                       // timing experiment: tables only
+    if (xflags & KXE_TABLES_ONLY) return 0;                       // timing experiment: tables only
     u8* const streamStart = op;
     u32* const cbuf = lds.u.seq.cbuf;
     for (int i = lane; i < 192; i += 64) cbuf[i] = 0;
@@ -1140,20 +1151,20 @@ KX_DEV void zstd_entropy_slice(const KEntropyArgs& a, KEntropyLds& lds, u32 slic
         const KSeq* const seqs = a.seqs + (size_t)slice * a.seq_cap;
         u8* const lits = a.lits + (size_t)slice * a.lit_cap;
         u32 const litSize = mm.litSize + mm.lastLL;
-        if (a.flags & 8u) kx_gather_literals(lits, src, n, seqs, mm.nbSeq, mm.longType, mm.longPos, lane);
+        if (a.flags & KXE_GATHER_LITS) kx_gather_literals(lits, src, n, seqs, mm.nbSeq, mm.longType, mm.longPos, lane);
         // complete the literal buffer with the trailing literals
         kx_wave_copy(lits + mm.litSize, src + (n - mm.lastLL), mm.lastLL, lane);
         kx_sync();
         bool const suspect = (mm.nbSeq == 0) || (litSize / mm.nbSeq >= 20);
         KHufPrev hp; hp.ct = nullptr; hp.valid = false; hp.newCt = nullptr; hp.outcome = 0;
         if (PRIOR) { hp.ct = a.prior->ct; hp.valid = a.prior->hufMode != 0; hp.complete = a.prior->hufMode == 2; }
-        u32 const litSec = (a.flags & 1u) ? 3u : kzstd_literals(lds, body, lits, litSize, suspect, a.scratch + (size_t)slice * a.scratch_words, lane, PRIOR ? &hp : nullptr, (a.flags & 64u) != 0);
+        u32 const litSec = (a.flags & KXE_NO_LIT_CODING) ? 3u : kzstd_literals(lds, body, lits, litSize, suspect, a.scratch + (size_t)slice * a.scratch_words, lane, PRIOR ? &hp : nullptr, (a.flags & KXE_RAW_LITS) != 0);
         kx_sync();
         // (levels 5 .. 10 pass the level in bits 12 ..: which of the strategies greedy / lazy / lazy2 a slice was parsed with follows from its size,
         // zstd_lazy.h kx_lazy_params; the sequence coder takes the strategy's number in bits 8 .. 10)
-        u32 xf = a.flags & 0xFFFu;
-        if (a.flags >> 12) { u32 const lvl = a.flags >> 12; xf |= (n <= 16384u ? (lvl == 4u ? 3u : lvl == 5u ? 4u : 5u) : (lvl == 4u ? 2u : lvl == 5u ? 3u : lvl == 6u ? 4u : 5u)) << 8; }
-        u32 const seqSec = (a.flags & 2u) ? 0u : kzstd_sequences(lds, body + litSec, seqs, mm.nbSeq, mm.longType, mm.longPos, lane, litSec < n ? n - litSec : 0u, xf, PRIOR ? a.prior : nullptr);
+        u32 xf = a.flags & KXE_XFLAGS_MASK;
+        if (a.flags >> KXE_LEVEL_SHIFT) { u32 const lvl = a.flags >> KXE_LEVEL_SHIFT; xf |= (n <= 16384u ? (lvl == 4u ? 3u : lvl == 5u ? 4u : 5u) : (lvl == 4u ? 2u : lvl == 5u ? 3u : lvl == 6u ? 4u : 5u)) << KXE_STRATEGY_SHIFT; }
+        u32 const seqSec = (a.flags & KXE_NO_SEQ_CODING) ? 0u : kzstd_sequences(lds, body + litSec, seqs, mm.nbSeq, mm.longType, mm.longPos, lane, litSec < n ? n - litSec : 0u, xf, PRIOR ? a.prior : nullptr);
         if (seqSec != 0) {
             cSize = litSec + seqSec;
             if (cSize >= n - kx_min_gain(n)) cSize = 0;
@@ -1185,7 +1196,7 @@ struct KFrameArgs {
     u32 level2;                              // 1: level 2's parameters (window 2^20 / 2^18 instead of 2^19 / level 3's)
     u32 fast_step0 = 0;                      // strategy 1 only: 0 = level 1 / 2; else a negative level: row 0 of libzstd's tables, a step of 1 - level, literals left raw
     u32 cls;                                 // which slices this launch takes (kx_in_class): a level-2 batch goes through both kernels
-    u32 stream;                              // 0: one-shot frames as ZSTD_compress2 writes them into a bound-sized buffer (size known, the
+    u32 stream;                              // KXF_* below.  0: one-shot frames as ZSTD_compress2 writes them into a bound-sized buffer (size known, the
                                              // caller's array compressed in place); 1: streaming frames (finish = false ... finish = true:
                                              // no content size, window 2^21, input taken in chunks of 128 KiB); 2: same, and the
                                              // closing call brought no data (an empty last block closes a frame that ends on a chunk boundary);
@@ -1193,9 +1204,10 @@ struct KFrameArgs {
                                              // max(8192, n / 10) bytes, below ZSTD_compressBound: size known, input staged in chunks of 128 KiB)
     u32 tail_direct;                         // streams: bytes the closing call brought onto an empty staging buffer with room for
                                              // their bound in its output slice (compressed in place as one chunk); else 0
-    u32 out_chunk;                           // stream == 3: size of the driver's output slices; 0 = the reference's max(8192, n / 10)
+    u32 out_chunk;                           // KXF_REFERENCE: size of the driver's output slices; 0 = the reference's max(8192, n / 10)
     u32* status_word = nullptr;              // the context's status word: bit 1 (KMP_STATUS_KERNEL_GUARD) when a block's parser tripped its loop guard
 };
+enum : u32 { KXF_ONE_SHOT = 0u, KXF_STREAM = 1u, KXF_STREAM_EMPTY_END = 2u, KXF_REFERENCE = 3u };      // KFrameArgs.stream
 
 // The block before fs.ipos is out: libzstd's staging buffer and window move on to the block that starts there
 // (ZSTD_compressStream_generic's buffered path, ZSTD_window_update per chunk, ZSTD_window_enforceMaxDist per block;
@@ -1204,10 +1216,10 @@ struct KFrameArgs {
 KX_DEV u32 kx_frame_window_step(KFrameState& fs, u32 n, u32 mode, u32 windowLog, u32 tailDirect, u32 outChunkArg)
 {
     u32 const maxDist = 1u << windowLog;
-    if (mode != 0 && fs.ipos == fs.chunkEnd) {
+    if (mode != KXF_ONE_SHOT && fs.ipos == fs.chunkEnd) {
         // a chunk of 128 KiB is done; the next one goes behind it in the staging buffer (window + 128 KiB bytes, the window
         // being the content size when that is known and smaller) or, when it would not fit, to the buffer's start
-        u32 const windowSize = (mode == 3 && n < maxDist) ? n : maxDist;
+        u32 const windowSize = (mode == KXF_REFERENCE && n < maxDist) ? n : maxDist;
         u32 const inBuffSize = windowSize + (KX_BLOCK_MAX < windowSize ? KX_BLOCK_MAX : windowSize);
         fs.bufPos += KX_BLOCK_MAX;
         if (fs.bufPos + KX_BLOCK_MAX > inBuffSize) { fs.extBase = fs.ipos - fs.bufPos; fs.bufPos = 0; }
@@ -1215,7 +1227,7 @@ KX_DEV u32 kx_frame_window_step(KFrameState& fs, u32 n, u32 mode, u32 windowLog,
         if (fs.bufPos == 0) {
             // empty staging buffer: if the current output slice has room for the bound of everything still to come,
             // libzstd compresses that rest where it lies (ZSTD_compressEnd), as one chunk
-            if (mode == 3) {
+            if (mode == KXF_REFERENCE) {
                 u32 const outChunk = outChunkArg ? outChunkArg : (n / 10u > 8192u ? n / 10u : 8192u);     // SliceTransform.kt:47-56
                 u32 const room = outChunk - fs.opos % outChunk, r = n - fs.ipos;       // every earlier call filled its slice
                 tail = room >= r + (r >> 8) + (r < KX_BLOCK_MAX ? (KX_BLOCK_MAX - r) >> 11 : 0u);
@@ -1313,8 +1325,8 @@ KX_DEV void zstd_frame_block(const KFrameArgs& a, KEntropyLds& lds, u32 slice, i
     u32 const n = a.in_len[slice];
     u8* const dst = a.dst + a.out_off[slice];
     u32* const hufct = a.hufct + (size_t)slice * 512u;
-    bool const streaming = a.stream == 1 || a.stream == 2;       // size unknown when the frame starts
-    bool const emptyEnd = a.stream == 2 && (n % KX_BLOCK_MAX) == 0;
+    bool const streaming = a.stream == KXF_STREAM || a.stream == KXF_STREAM_EMPTY_END;       // size unknown when the frame starts
+    bool const emptyEnd = a.stream == KXF_STREAM_EMPTY_END && (n % KX_BLOCK_MAX) == 0;
     // the window a frame of known size is written with: level 3's 2^21 at most, or the "fast" level's own (2^19 / 2^20), past which the
     // header carries a window descriptor instead of the single-segment flag
     u32 const fastLevel = a.fast_step0 ? 0u : a.level2 ? 2u : 1u;

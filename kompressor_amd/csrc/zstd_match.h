@@ -30,10 +30,7 @@ struct KMatchArgs {
     u32* tables;                     // per team: KX_TBL_ENTRIES
     u32* team_epoch;                 // per team
     u32* counter;                    // work queue head (zeroed by the host)
-    u32 flags;                       // 1 = non-temporal table loads, 2 = non-temporal table stores (the default),
-                                     // 4 = copy no literals (the entropy kernel gathers them; A/B switch),
-                                     // 8 = block mode with the parameters of a stream of unknown size,
-                                     // 16 = block mode, slices of 4 MiB and more: table entries are plain 32-bit indices
+    u32 flags;                       // KXM_* below
     // block mode (frames of several blocks): one block of every unfinished slice per launch
     const KFrameState* fstate;       // per slice
     u32* big_tables;                 // per slice: KX_BIG_TBL_ENTRIES
@@ -46,6 +43,21 @@ struct KMatchArgs {
     // a piece of a batch on a stream of its own (kmp_zstd_compress_batch_pieces): this launch's workgroups own the teams from
     // block_base * (64 / G) on, so that the pieces of one batch run side by side over disjoint team tables
     u32 block_base = 0;
+};
+
+// KMatchArgs.flags (every parser: zstd_match*.h; KFastArgs.m / KDictArgs.m / KBigArgs.m carry the same word)
+enum : u32 {
+    KXM_NT_LOADS      = 1u,          // non-temporal table loads (experiment)
+    KXM_NT_STORES     = 2u,          // non-temporal table stores (the default)
+    KXM_NO_LITS       = 4u,          // copy no literals: the entropy kernel gathers them (KXE_GATHER_LITS; the default)
+    KXM_STREAM_PARAMS = 8u,          // block mode: the parameters of a stream of unknown size (window 2^21; the fast rows' own)
+    KXM_WIDE          = 16u,         // block mode, slices of 4 MiB and more: table entries are plain 32-bit indices, no check bits
+    KXM_L2_DFAST      = 32u,         // block mode: level 2's double-fast row (its slices of 128 .. 256 KiB, sizes known)
+    KXM_CLASS_SHIFT   = 6u,          // block mode, two bits: which slices this launch takes (kx_in_class: 0 all, 1 only those of
+    KXM_CLASS_MASK    = 3u,          //   128 .. 256 KiB, 2 only the others); a level-2 batch goes through both block-chain kernels
+    KXM_ADAPTIVE      = 128u,        // one-block mode (experiment): the speculation width follows the last hit.  The same bit as the
+                                     //   class field's upper one: the two modes never meet in one launch
+    KXM_TIMESTAMPS    = 256u,        // one-block mode (diagnostics): when each slice was done, into its record's padding
 };
 
 KX_DEV u32* kx_team_tables(const KMatchArgs& a, u32 team)
@@ -144,7 +156,7 @@ template <int G, bool BLK = false, class DONE = KNoDone>
 KX_DEV void zstd_match_body(const KMatchArgs& a, DONE const& done = DONE())
 {
     constexpr int NT = 64 / G;
-    bool const wide = BLK && (a.flags & 16u);               // entries without check bits (indices need all 32 bits)
+    bool const wide = BLK && (a.flags & KXM_WIDE);               // entries without check bits (indices need all 32 bits)
     u32 const IDXM = BLK ? (wide ? 0xFFFFFFFFu : KX_BLK_IDX_MASK) : KX_IDX_MASK;
     constexpr u32 TAGM = BLK ? 0u : KX_TAG_MASK;            // block mode: no epoch (tag stays 0)
     constexpr u32 CHKS = BLK ? KX_BLK_IDX_BITS : KX_CHK_SHIFT;
@@ -173,9 +185,9 @@ KX_DEV void zstd_match_body(const KMatchArgs& a, DONE const& done = DONE())
     u64 sq0 = 0, sq1 = 0;
     // long-table lookup of the first position of the next step, when the last step's extra lane already made it
     bool carry = false; u32 carry_idxl = 0;
-    // flags bit 7 (experiment): the speculation width follows the last hit -- after a hit at lane w the next step looks at
+    // KXM_ADAPTIVE (experiment): the speculation width follows the last hit -- after a hit at lane w the next step looks at
     // w + 1 positions, after a step without a hit at all G - 1 again: the probes of lanes behind a winner are reads that buy nothing
-    int kmax = G - 1; bool const adaptive = !BLK && (a.flags & 128u) != 0;
+    int kmax = G - 1; bool const adaptive = !BLK && (a.flags & KXM_ADAPTIVE) != 0;
     // Loads that depend on the new position only are requested together, in the repcode-check block: the bytes of the immediate
     // repcode test, the bytes of the complementary inserts of the match that just ended (compl_due; wa = the bytes at its
     // search position + 2, requested when the match was taken) and the words of the first search step (pw: lane k's
@@ -201,11 +213,11 @@ KX_DEV void zstd_match_body(const KMatchArgs& a, DONE const& done = DONE())
                 else if (BLK) {
                     KFrameState const fs = a.fstate[s];
                     bool ok4 = true;
-                    KParams P0 = (a.flags & 32u) ? kx_params_l2_dfast() : (a.level == 4u) ? kx_params_l4(a.in_len[s], ok4) : kx_params_l3(a.in_len[s]);          // (flags bit 5: level 2's double-fast row)
-                    if (a.flags & 8u) { P0.windowLog = 21; P0.chainLog = a.level == 4u ? 18 : 16; P0.hashLog = a.level == 4u ? 18 : 17; P0.minMatch = 5; }   // streaming frame: size unknown when it starts
+                    KParams P0 = (a.flags & KXM_L2_DFAST) ? kx_params_l2_dfast() : (a.level == 4u) ? kx_params_l4(a.in_len[s], ok4) : kx_params_l3(a.in_len[s]);          // (level 2's double-fast row)
+                    if (a.flags & KXM_STREAM_PARAMS) { P0.windowLog = 21; P0.chainLog = a.level == 4u ? 18 : 16; P0.hashLog = a.level == 4u ? 18 : 17; P0.minMatch = 5; }   // streaming frame: size unknown when it starts
                     KBlockWin const bw = kx_block_window(fs.lowLimit, fs.dictLimit, fs.ipos, fs.blockSize, P0.windowLog);
                     // (a block that libzstd parses with the extDict variant is left to zstd_match_ext_body)
-                    if (fs.blockSize != 0 && !bw.ext && kx_in_class((a.flags >> 6) & 3u, a.in_len[s])) {           // else: frame finished (or not this launch's), fetch the next slice
+                    if (fs.blockSize != 0 && !bw.ext && kx_in_class((a.flags >> KXM_CLASS_SHIFT) & KXM_CLASS_MASK, a.in_len[s])) {           // else: frame finished (or not this launch's), fetch the next slice
                         slice = s;
                         src = a.src + a.in_off[s];
                         seqs = a.seqs + (size_t)s * a.seq_cap; lits = a.lits + (size_t)s * a.lit_cap;
@@ -305,7 +317,7 @@ KX_DEV void zstd_match_body(const KMatchArgs& a, DONE const& done = DONE())
                 hl = kx_hash_long(w, hbL); hs = kx_hash_short(w, hbS, mls);
                 // the lane after the last candidate only provides the long-table lookup of "ip1"
                 bool const haveL = carry && k == 0;
-                if (a.flags & 1u) { if (!haveL) el = kx_ld_nt(&L[hl]); if (cand) es = kx_ld_nt(&S[hs]); }
+                if (a.flags & KXM_NT_LOADS) { if (!haveL) el = kx_ld_nt(&L[hl]); if (cand) es = kx_ld_nt(&S[hs]); }
                 else { if (!haveL) el = L[hl]; if (cand) es = S[hs]; }
                 KX_STAT(8, haveL ? 0 : 1); KX_STAT(9, cand ? 1 : 0);      // table probes issued (long, short)
             }
@@ -375,7 +387,7 @@ KX_DEV void zstd_match_body(const KMatchArgs& a, DONE const& done = DONE())
             if (ins) {
                 KX_STAT(10, (supL ? 0 : 1) + (supS ? 0 : 1));             // inserts of searched positions
                 u32 const v = tag | (u32)(pos + 2);
-                if (a.flags & 2u) { if (!supL) kx_st_nt(&L[hl], v | ckl); if (!supS) kx_st_nt(&S[hs], v | cks); }
+                if (a.flags & KXM_NT_STORES) { if (!supL) kx_st_nt(&L[hl], v | ckl); if (!supS) kx_st_nt(&S[hs], v | cks); }
                 else { if (!supL) L[hl] = v | ckl; if (!supS) S[hs] = v | cks; }
             }
 
@@ -454,7 +466,7 @@ KX_DEV void zstd_match_body(const KMatchArgs& a, DONE const& done = DONE())
                 if (bw) { m_start -= (int)back; m_mpos -= (int)back; lenA += back; off2 = off1; off1 = m_off; offBase = m_off + 3; }
                 else if (m_type == KMT_REP0) { u32 const t = off2; off2 = off1; off1 = t; }
                 int const ll = m_start - anchor;
-                if (!(a.flags & 4u)) for (int c = 8 * k; c < ll; c += 8 * G) kx_st64(lits + nlit + c, kx_ld64_clamped(src, anchor + c, n));
+                if (!(a.flags & KXM_NO_LITS)) for (int c = 8 * k; c < ll; c += 8 * G) kx_st64(lits + nlit + c, kx_ld64_clamped(src, anchor + c, n));
                 {
                     u64 const q = (u64)offBase | ((u64)(u16)ll << 32) | ((u64)(u16)(lenA - 3) << 48);   // KSeq
                     u32 const slot = nseq & (2u * G - 1u);
@@ -487,7 +499,7 @@ KX_DEV void zstd_match_body(const KMatchArgs& a, DONE const& done = DONE())
                     KSliceMeta mm;
                     mm.nbSeq = nseq; mm.litSize = nlit; mm.lastLL = (u32)(n - anchor);
                     mm.longType = longType; mm.longPos = longPos; mm.status = status; mm.pad[0] = 0; mm.pad[1] = 0;
-                    if (!BLK && (a.flags & 256u)) { u64 const t = kx_realtime(); mm.pad[0] = (u32)t; mm.pad[1] = (u32)(t >> 32); }   // diagnostics: when the slice was done (100 MHz ticks)
+                    if (!BLK && (a.flags & KXM_TIMESTAMPS)) { u64 const t = kx_realtime(); mm.pad[0] = (u32)t; mm.pad[1] = (u32)(t >> 32); }   // diagnostics: when the slice was done (100 MHz ticks)
                     if (BLK) {
                         // repcodes this block leaves behind (taken over by the frame only if the block is emitted compressed)
                         u32 const s2 = (saved1 != 0 && off1 != 0) ? saved1 : saved2;

@@ -75,7 +75,7 @@ KX_DEV void zstd_match2_body(const KMatchArgs& a)
     u32* const L = kx_team_tables(a, team);
     u32* const S = L + KX_TBL_LONG;
     u64 const tmask = (1ull << G) - 1ull;
-    bool const nt_st = (a.flags & 2u) != 0;
+    bool const nt_st = (a.flags & KXM_NT_STORES) != 0;
 
     // ---- team state (uniform across the team's lanes) -------------------
     int state = K2_IDLE;

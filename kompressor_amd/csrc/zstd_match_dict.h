@@ -3,7 +3,7 @@
 // ZSTD_CCtx_loadDictionary, then the one-shot ZSTD_compressStream2 at :112).
 //
 // libzstd 1.5.7 turns the dictionary into a CDict (tables sized for the dictionary, built once: here by the host,
-// kmp_api.hip) and then parses every input with one of two double-fast variants, both a plain position-by-position
+// kmp_batch.hip) and then parses every input with one of two double-fast variants, both a plain position-by-position
 // loop (no pipelined look-ahead as in the dictionary-less parser):
 //   * input <= 16 KiB: the CDict stays attached; its (tagged) tables are consulted when the working tables miss
 //     ("dictMatchState");

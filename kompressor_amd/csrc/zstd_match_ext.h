@@ -25,7 +25,7 @@ KX_DEV void zstd_match_ext_body(const KMatchArgs& a)
     int const k = lane & (G - 1);
     int const tbase = lane - k;
     u64 const tmask = (G == 64) ? ~0ull : ((1ull << G) - 1ull);
-    bool const wide = (a.flags & 16u) != 0;
+    bool const wide = (a.flags & KXM_WIDE) != 0;
     u32 const IDXM = wide ? 0xFFFFFFFFu : KX_BLK_IDX_MASK;
     constexpr u32 CHKS = KX_BLK_IDX_BITS;
 
@@ -49,7 +49,7 @@ KX_DEV void zstd_match_ext_body(const KMatchArgs& a)
                     KFrameState const fs = a.fstate[s];
                     bool ok4 = true;
                     KParams P = (a.level == 4u) ? kx_params_l4(a.in_len[s], ok4) : kx_params_l3(a.in_len[s]);
-                    if (a.flags & 8u) { P.windowLog = 21; P.chainLog = a.level == 4u ? 18 : 16; P.hashLog = a.level == 4u ? 18 : 17; P.minMatch = 5; }
+                    if (a.flags & KXM_STREAM_PARAMS) { P.windowLog = 21; P.chainLog = a.level == 4u ? 18 : 16; P.hashLog = a.level == 4u ? 18 : 17; P.minMatch = 5; }
                     KBlockWin const bw = kx_block_window(fs.lowLimit, fs.dictLimit, fs.ipos, fs.blockSize, P.windowLog);
                     if (fs.blockSize != 0 && bw.ext) {
                         slice = s;
@@ -157,7 +157,7 @@ KX_DEV void zstd_match_ext_body(const KMatchArgs& a)
                 if (m_back) { m_start -= (int)back; lenA += back; off2 = off1; off1 = m_off; offBase = m_off + 3; }
                 int const ll = m_start - anchor;
                 // the literals in front of the match (the block-chain kernel codes them from this buffer)
-                if (!(a.flags & 4u)) for (int c = 8 * k; c < ll; c += 8 * G) kx_st64(lits + nlit + c, kx_ld64_clamped(src, anchor + c, n));
+                if (!(a.flags & KXM_NO_LITS)) for (int c = 8 * k; c < ll; c += 8 * G) kx_st64(lits + nlit + c, kx_ld64_clamped(src, anchor + c, n));
                 {
                     u64 const q = (u64)offBase | ((u64)(u16)ll << 32) | ((u64)(u16)(lenA - 3) << 48);   // KSeq
                     u32 const slot = nseq & (2u * G - 1u);

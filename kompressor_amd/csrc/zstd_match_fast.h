@@ -8,7 +8,7 @@
 #pragma once
 #include "zstd_match.h"
 
-struct KFastArgs { KMatchArgs m; u32 level; u32 step0 = 2; };     // level 1 or 2 (block mode: level 1; m.flags bit 8 = stream of unknown size), or 0 = a negative
+struct KFastArgs { KMatchArgs m; u32 level; u32 step0 = 2; };     // level 1 or 2 (block mode: level 1; m.flags & KXM_STREAM_PARAMS = stream of unknown size), or 0 = a negative
                                                                   // level (row 0 of libzstd's tables) with step0 = 1 - level (ZSTD_compressBlock_fast: targetLength + 1)
 
 // ZSTD_getCParams(level, n, 0) for the fast rows: windowLog, hashLog, minMatch
@@ -46,7 +46,7 @@ enum { KFS_IDLE = 0, KFS_START = 1, KFS_PAIR = 2, KFS_REPLOOP = 3, KFS_MATCH = 4
 template <int G, bool BLK = false>
 KX_DEV void zstd_match_fast_body(const KFastArgs& f)
 {
-    bool const wide = BLK && (f.m.flags & 16u);             // slices of 4 MiB and more: plain 32-bit indices, no check bits
+    bool const wide = BLK && (f.m.flags & KXM_WIDE);             // slices of 4 MiB and more: plain 32-bit indices, no check bits
     u32 const IDXM = BLK ? (wide ? 0xFFFFFFFFu : KX_BLK_IDX_MASK) : KX_IDX_MASK;
     constexpr u32 TAGM = BLK ? 0u : KX_TAG_MASK;            // block mode: plain indices, no epoch
     u32 const CHKM = BLK ? (wide ? 0u : KX_BLK_CHK_MASK) : KX_CHK_MASK;      // check bits (first 4 bytes of the position, what a candidate is compared on)
@@ -87,14 +87,14 @@ KX_DEV void zstd_match_fast_body(const KFastArgs& f)
                 else if (BLK) {
                     KFrameState const fs = a.fstate[s];
                     // (a block that libzstd parses with the extDict variant -- behind a wrap of its staging buffer -- is left to zstd_match_fast_ext_body)
-                    KBlockWin const bw = kx_block_window(fs.lowLimit, fs.dictLimit, fs.ipos, fs.blockSize, kx_window_log_fast(f.level, a.in_len[s], (a.flags & 8u) != 0));
-                    if (fs.blockSize != 0 && !bw.ext && kx_in_class((a.flags >> 6) & 3u, a.in_len[s])) {
+                    KBlockWin const bw = kx_block_window(fs.lowLimit, fs.dictLimit, fs.ipos, fs.blockSize, kx_window_log_fast(f.level, a.in_len[s], (a.flags & KXM_STREAM_PARAMS) != 0));
+                    if (fs.blockSize != 0 && !bw.ext && kx_in_class((a.flags >> KXM_CLASS_SHIFT) & KXM_CLASS_MASK, a.in_len[s])) {
                         slice = s;
                         src = a.src + a.in_off[s];
                         seqs = a.seqs + (size_t)s * a.seq_cap;
                         H = a.big_tables + (size_t)s * KX_BIG_TBL_ENTRIES;
                         kx_params_fast(f.level, a.in_len[s], hlog, mls);
-                        if (a.flags & 8u) { hlog = f.level == 2 ? 16 : f.level == 0 ? 13 : 14; mls = f.level == 1 ? 7 : 6; }      // size unknown: level 1 window 19, hash 14, minMatch 7; level 2 window 20, hash 16, minMatch 6; negative levels window 19, hash 13, minMatch 6
+                        if (a.flags & KXM_STREAM_PARAMS) { hlog = f.level == 2 ? 16 : f.level == 0 ? 13 : 14; mls = f.level == 1 ? 7 : 6; }      // size unknown: level 1 window 19, hash 14, minMatch 7; level 2 window 20, hash 16, minMatch 6; negative levels window 19, hash 13, minMatch 6
                         nseq = 0; nlit = 0; longType = 0; longPos = 0; guard = 0; status = 0; tag = 0;
                         bstart = (int)fs.ipos; n = bstart + (int)fs.blockSize;   // n = end of the block
                         anchor = bstart; ilimit = n - 8;
@@ -343,7 +343,7 @@ template <int G>
 KX_DEV void zstd_match_fast_ext_body(const KFastArgs& f)
 {
     const KMatchArgs& a = f.m;
-    bool const wide = (a.flags & 16u) != 0;
+    bool const wide = (a.flags & KXM_WIDE) != 0;
     u32 const IDXM = wide ? 0xFFFFFFFFu : KX_BLK_IDX_MASK;
 #define KFX_E(bytes4_, idx_) ((u32)(idx_) | (wide ? 0u : kx_chk_short((u64)(bytes4_)) << KX_BLK_IDX_BITS))
     int const lane = kx_lane();
@@ -370,14 +370,14 @@ KX_DEV void zstd_match_fast_ext_body(const KFastArgs& f)
                 if (s >= a.n_slices) state = KFX_DONE;
                 else {
                     KFrameState const fs = a.fstate[s];
-                    KBlockWin const bw = kx_block_window(fs.lowLimit, fs.dictLimit, fs.ipos, fs.blockSize, kx_window_log_fast(f.level, a.in_len[s], (a.flags & 8u) != 0));
-                    if (fs.blockSize != 0 && bw.ext && kx_in_class((a.flags >> 6) & 3u, a.in_len[s])) {
+                    KBlockWin const bw = kx_block_window(fs.lowLimit, fs.dictLimit, fs.ipos, fs.blockSize, kx_window_log_fast(f.level, a.in_len[s], (a.flags & KXM_STREAM_PARAMS) != 0));
+                    if (fs.blockSize != 0 && bw.ext && kx_in_class((a.flags >> KXM_CLASS_SHIFT) & KXM_CLASS_MASK, a.in_len[s])) {
                         slice = s;
                         src = a.src + a.in_off[s];
                         seqs = a.seqs + (size_t)s * a.seq_cap;
                         H = a.big_tables + (size_t)s * KX_BIG_TBL_ENTRIES;
                         kx_params_fast(f.level, a.in_len[s], hlog, mls);
-                        if (a.flags & 8u) { hlog = f.level == 2 ? 16 : f.level == 0 ? 13 : 14; mls = f.level == 1 ? 7 : 6; }
+                        if (a.flags & KXM_STREAM_PARAMS) { hlog = f.level == 2 ? 16 : f.level == 0 ? 13 : 14; mls = f.level == 1 ? 7 : 6; }
                         dsi = bw.dictStartIndex; psi = bw.prefixStartIndex;
                         nseq = 0; nlit = 0; longType = 0; longPos = 0; guard = 0; status = 0;
                         ip0 = (int)fs.ipos; anchor = ip0; n = ip0 + (int)fs.blockSize; ilimit = n - 8;

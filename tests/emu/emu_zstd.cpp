@@ -1,53 +1,56 @@
-// TEST INFRASTRUCTURE: runs the product kernel bodies on the CPU wave emulator.
+// TEST INFRASTRUCTURE: runs the product kernel bodies on the CPU wave emulator.  Workspace sizes, batch views and the kernels' argument
+// structs come from the product's own launch description (zstd_launch.h); what is restated here is the sequence of launches only.
 #include "kx_wave.h"
 #include "emu_core.h"
-#include "zstd_match.h"
+#include "zstd_launch.h"
 #include <stdlib.h>
 #include <vector>
+
+namespace {
+bool env_on(const char* name) { return getenv(name) && atoi(getenv(name)) != 0; }
+bool team_width_ok(int G) { return G == 2 || G == 4 || G == 8 || G == 16 || G == 32 || G == 64; }
+// a context's workspace for n slices of up to block_cap bytes, full of junk no kernel may rely on
+struct Work {
+    KWorkCaps cap; std::vector<KSeq> seqs; std::vector<u8> lits; std::vector<KSliceMeta> meta; std::vector<u32> scratch;
+    Work(u32 n, u32 block_cap) : cap(kx_work_caps(block_cap)), seqs((size_t)n * cap.seq_cap), lits((size_t)n * cap.lit_cap, 0xEE), meta(n), scratch((size_t)n * cap.scratch_words, 0xA5A5A5A5u) {}
+    KBatchView view(const u8* src, const u64* in_off, const u32* in_len, u32 n, u8* dst, const u64* out_off, u32* out_len)
+    { KBatchView v = { src, in_off, in_len, dst, out_off, out_len, n, seqs.data(), lits.data(), meta.data(), scratch.data(), cap }; return v; }
+};
+// team tables for a launch of nblocks waves: stale junk with epoch 0 in every entry, every team at start_epoch
+struct Teams {
+    std::vector<u32> tables, epoch; bool level4;
+    Teams(u32 nblocks, int G, u32 start_epoch, bool l4 = false) : tables((size_t)nblocks * (64 / G) * (l4 ? KX_TBL4_ENTRIES : KX_TBL_ENTRIES), 0xDEADBEEFu & 0x0003FFFFu), epoch(nblocks * (64 / G), start_epoch), level4(l4) {}
+    KTeamTables get() { return kx_one_piece(tables.data(), epoch.data(), level4); }
+};
+bool any_status(const KSliceMeta* meta, u32 n) { for (u32 i = 0; i < n; i++) if (meta[i].status) return true; return false; }
+// the level-3 parse of a view's slices: zstd_match.h, or the split-phase parser (ring = bytes of a team's window in LDS)
+int run_match(KBatchView const& v, KTeamTables const& t, int G, u32 nblocks, u32 flags)
+{
+    if (!team_width_ok(G)) return -2;
+    u32 counter = 0;
+    KMatchArgs const a = kx_match_args(v, t, &counter, flags);
+    kxemu::failed = 0;
+    by_team_width(G, [&](auto w) { kxemu::launch(nblocks, [&]() { zstd_match_body<decltype(w)::value>(a); }); });
+    return kxemu::failed ? -1 : 0;
+}
+}
 
 extern "C" __attribute__((visibility("default")))
 int emu_zstd_match(const u8* src, const u64* in_off, const u32* in_len, u32 n, int G, u32 nblocks,
                    KSeq* seqs, u32 seq_cap, u8* lits, u32 lit_cap, KSliceMeta* meta, u32 start_epoch)
 {
-    u32 const nteams = nblocks * (64 / G);
-    bool const l4 = getenv("KXEMU_LEVEL") && atoi(getenv("KXEMU_LEVEL")) == 4;          // level 4's double-fast row: larger tables
-    std::vector<u32> tables((size_t)nteams * (l4 ? KX_TBL4_ENTRIES : KX_TBL_ENTRIES), 0xDEADBEEFu & 0x0003FFFFu);   // stale junk with epoch 0
-    std::vector<u32> epoch(nteams, start_epoch);
-    u32 counter = 0;
-    KMatchArgs a;
-    a.src = src; a.in_off = in_off; a.in_len = in_len; a.n_slices = n;
-    a.seqs = seqs; a.seq_cap = seq_cap; a.lits = lits; a.lit_cap = lit_cap; a.meta = meta;
-    a.tables = tables.data(); a.team_epoch = epoch.data(); a.counter = &counter; a.flags = 0; a.fstate = nullptr; a.big_tables = nullptr;
-    if (l4) { a.tbl_stride = KX_TBL4_ENTRIES; a.tbl_long = KX_TBL4_LONG; a.level = 4; }
-    if (getenv("KXEMU_MATCH_FLAGS")) a.flags |= (u32)atoi(getenv("KXEMU_MATCH_FLAGS")) & 128u;       // (bit 7: adaptive speculation width)
-    kxemu::failed = 0;
-    switch (G) {
-    case 2:  kxemu::launch(nblocks, [&]() { zstd_match_body<2>(a); }); break;
-    case 4:  kxemu::launch(nblocks, [&]() { zstd_match_body<4>(a); }); break;
-    case 8:  kxemu::launch(nblocks, [&]() { zstd_match_body<8>(a); }); break;
-    case 16: kxemu::launch(nblocks, [&]() { zstd_match_body<16>(a); }); break;
-    case 32: kxemu::launch(nblocks, [&]() { zstd_match_body<32>(a); }); break;
-    case 64: kxemu::launch(nblocks, [&]() { zstd_match_body<64>(a); }); break;
-    default: return -2;
-    }
-    return kxemu::failed ? -1 : 0;
+    if (!team_width_ok(G)) return -2;
+    Teams teams(nblocks, G, start_epoch, getenv("KXEMU_LEVEL") && atoi(getenv("KXEMU_LEVEL")) == 4);      // level 4's double-fast row: larger tables
+    KBatchView const v = { src, in_off, in_len, nullptr, nullptr, nullptr, n, seqs, lits, meta, nullptr, { seq_cap, lit_cap, 0, 0 } };
+    return run_match(v, teams.get(), G, nblocks, getenv("KXEMU_MATCH_FLAGS") ? (u32)atoi(getenv("KXEMU_MATCH_FLAGS")) & KXM_ADAPTIVE : 0u);
 }
 
 #include "zstd_match2.h"
-// The split-phase parser (zstd_match2.h): same interface, same results.  ring = bytes of a team's window in LDS.
-extern "C" __attribute__((visibility("default")))
-int emu_zstd_match2(const u8* src, const u64* in_off, const u32* in_len, u32 n, int G, u32 nblocks,
-                    KSeq* seqs, u32 seq_cap, u8* lits, u32 lit_cap, KSliceMeta* meta, u32 start_epoch)
+static int run_match2(KBatchView const& v, KTeamTables const& t, int G, u32 nblocks, u32 flags)
 {
     int const ring = getenv("KXEMU_RING") ? atoi(getenv("KXEMU_RING")) : 256;
-    u32 const nteams = nblocks * (64 / G);
-    std::vector<u32> tables((size_t)nteams * KX_TBL_ENTRIES, 0xDEADBEEFu & 0x0003FFFFu);   // stale junk with epoch 0
-    std::vector<u32> epoch(nteams, start_epoch);
     u32 counter = 0;
-    KMatchArgs a;
-    a.src = src; a.in_off = in_off; a.in_len = in_len; a.n_slices = n;
-    a.seqs = seqs; a.seq_cap = seq_cap; a.lits = lits; a.lit_cap = lit_cap; a.meta = meta;
-    a.tables = tables.data(); a.team_epoch = epoch.data(); a.counter = &counter; a.flags = 0; a.fstate = nullptr; a.big_tables = nullptr;
+    KMatchArgs const a = kx_match_args(v, t, &counter, flags);
     kxemu::failed = 0;
     switch (G * 1000 + ring) {
     case 2256:  kxemu::launch(nblocks, [&]() { zstd_match2_body<2, 256>(a); }); break;
@@ -58,113 +61,93 @@ int emu_zstd_match2(const u8* src, const u64* in_off, const u32* in_len, u32 n, 
     }
     return kxemu::failed ? -1 : 0;
 }
+// The split-phase parser (zstd_match2.h): same interface, same results.
+extern "C" __attribute__((visibility("default")))
+int emu_zstd_match2(const u8* src, const u64* in_off, const u32* in_len, u32 n, int G, u32 nblocks,
+                    KSeq* seqs, u32 seq_cap, u8* lits, u32 lit_cap, KSliceMeta* meta, u32 start_epoch)
+{
+    if (G != 2 && G != 4 && G != 8) return -2;
+    Teams teams(nblocks, G, start_epoch);
+    KBatchView const v = { src, in_off, in_len, nullptr, nullptr, nullptr, n, seqs, lits, meta, nullptr, { seq_cap, lit_cap, 0, 0 } };
+    return run_match2(v, teams.get(), G, nblocks, 0u);
+}
 
-#include "zstd_entropy.h"
-
-// Full compress pipeline (match kernel + entropy kernel) on the emulator.
+// Full compress pipeline (match kernel + entropy kernel) on the emulator: zstd_compress_dfast's steps.  A batch of two slices or more goes
+// through in two chunks over the one workspace, as the product's large batches do; there the entropy launch of the first chunk runs beside
+// the parse of the second, here behind it.
 extern "C" __attribute__((visibility("default")))
 int emu_zstd_compress(const u8* src, const u64* in_off, const u32* in_len, u32 n, int G, u32 nblocks,
                       u8* dst, const u64* out_off, u32* out_len, u32 slice_cap)
 {
-    u32 const seq_cap = (slice_cap / 4 + 8 + 15) & ~15u, lit_cap = slice_cap + 64, scratch_words = slice_cap / 4 + 64;
-    std::vector<KSeq> seqs((size_t)n * seq_cap);
-    std::vector<u8> lits((size_t)n * lit_cap, 0xEE);
-    std::vector<KSliceMeta> meta(n);
-    std::vector<u32> scratch((size_t)n * scratch_words, 0xA5A5A5A5u);
-    // KXEMU_MATCH_V2=1: the split-phase parser (zstd_match2.h; it copies no literals, the entropy kernel gathers them)
-    bool const v2 = getenv("KXEMU_MATCH_V2") && atoi(getenv("KXEMU_MATCH_V2")) != 0;
+    if (!team_width_ok(G)) return -2;
+    Work w(n, slice_cap);
+    KBatchView const v = w.view(src, in_off, in_len, n, dst, out_off, out_len);
+    bool const l4 = getenv("KXEMU_LEVEL") && atoi(getenv("KXEMU_LEVEL")) == 4;
+    Teams teams(nblocks, G, 7, l4);
     // KXEMU_FUSE=1: k_zstd_l3_fused's body (the entropy stage inside the parse kernel's waves)
-    if (getenv("KXEMU_FUSE") && atoi(getenv("KXEMU_FUSE")) != 0 && (G == 4 || G == 8)) {
-        u32 const nteams = nblocks * (64 / G);
-        std::vector<u32> tables((size_t)nteams * KX_TBL_ENTRIES, 0xDEADBEEFu & 0x0003FFFFu);
-        std::vector<u32> epoch(nteams, 7);
+    if (env_on("KXEMU_FUSE") && (G == 4 || G == 8)) {
         u32 counter = 0;
-        KMatchArgs a;
-        a.src = src; a.in_off = in_off; a.in_len = in_len; a.n_slices = n;
-        a.seqs = seqs.data(); a.seq_cap = seq_cap; a.lits = lits.data(); a.lit_cap = lit_cap; a.meta = meta.data();
-        a.tables = tables.data(); a.team_epoch = epoch.data(); a.counter = &counter; a.flags = 0; a.fstate = nullptr; a.big_tables = nullptr;
-        KEntropyArgs e;
-        e.src = src; e.in_off = in_off; e.in_len = in_len; e.n_slices = n;
-        e.seqs = seqs.data(); e.seq_cap = seq_cap; e.lits = lits.data(); e.lit_cap = lit_cap; e.meta = meta.data();
-        e.scratch = scratch.data(); e.scratch_words = scratch_words;
-        e.dst = dst; e.out_off = out_off; e.out_len = out_len; e.flags = 0u;
+        KMatchArgs const a = kx_match_args(v, kx_one_piece(teams.tables.data(), teams.epoch.data()), &counter, 0u);
+        KEntropyArgs const e = kx_entropy_args(v, kx_entropy_flags_dfast(a.flags, false));
         kxemu::failed = 0;
         if (G == 4) kxemu::launch(nblocks, [&]() { zstd_l3_fused_body<4>(a, e); });
         else kxemu::launch(nblocks, [&]() { zstd_l3_fused_body<8>(a, e); });
         if (kxemu::failed) return -1;
-        for (u32 i = 0; i < n; i++) if (meta[i].status) return -3;
-        return 0;
+        return any_status(v.meta, n) ? -3 : 0;
     }
-    int r = v2 ? emu_zstd_match2(src, in_off, in_len, n, G, nblocks, seqs.data(), seq_cap, lits.data(), lit_cap, meta.data(), 7)
-               : emu_zstd_match(src, in_off, in_len, n, G, nblocks, seqs.data(), seq_cap, lits.data(), lit_cap, meta.data(), 7);
-    if (r) return r;
-    for (u32 i = 0; i < n; i++) if (meta[i].status) return -3;
-    KEntropyArgs e;
-    e.src = src; e.in_off = in_off; e.in_len = in_len; e.n_slices = n;
-    e.seqs = seqs.data(); e.seq_cap = seq_cap; e.lits = lits.data(); e.lit_cap = lit_cap; e.meta = meta.data();
-    e.scratch = scratch.data(); e.scratch_words = scratch_words;
-    e.dst = dst; e.out_off = out_off; e.out_len = out_len; e.flags = v2 ? 8u : 0u;
+    // KXEMU_MATCH_V2=1: the split-phase parser (zstd_match2.h; it copies no literals, the entropy kernel gathers them)
+    bool const v2 = env_on("KXEMU_MATCH_V2");
+    u32 const match_flags = (v2 ? KXM_NO_LITS : 0u) | (getenv("KXEMU_MATCH_FLAGS") ? (u32)atoi(getenv("KXEMU_MATCH_FLAGS")) & KXM_ADAPTIVE : 0u);
+    u32 const starts[3] = { 0, n >= 2 ? n / 2 : n, n };
+    for (u32 ci = 0; ci < 2; ci++) {
+        KBatchView const cv = v.sub(starts[ci], starts[ci + 1] - starts[ci]);
+        if (cv.n == 0) continue;
+        int const r = v2 ? run_match2(cv, teams.get(), G, nblocks, match_flags) : run_match(cv, teams.get(), G, nblocks, match_flags);
+        if (r) return r;
+    }
+    if (any_status(v.meta, n)) return -3;
     kxemu::failed = 0;
-    kxemu::launch(nblocks, [&]() { zstd_entropy_body(e); });
+    for (u32 ci = 0; ci < 2; ci++) {
+        KBatchView const cv = v.sub(starts[ci], starts[ci + 1] - starts[ci]);
+        if (cv.n == 0) continue;
+        KEntropyArgs const e = kx_entropy_args(cv, kx_entropy_flags_dfast(match_flags, l4));
+        kxemu::launch(nblocks, [&]() { zstd_entropy_body(e); });
+    }
     return kxemu::failed ? -1 : 0;
 }
 
-#include "zstd_match_fast.h"
-// Levels 1 and 2 (strategy fast): fast match kernel + entropy kernel on the emulator.
+// Levels 1 and 2 (strategy fast) and the negative ones: fast match kernel + entropy kernel on the emulator.
 extern "C" __attribute__((visibility("default")))
 int emu_zstd_compress_level(const u8* src, const u64* in_off, const u32* in_len, u32 n, int G, u32 nblocks,
                             u8* dst, const u64* out_off, u32* out_len, u32 slice_cap, int level)
 {
-    u32 const seq_cap = (slice_cap / 4 + 8 + 15) & ~15u, lit_cap = slice_cap + 64, scratch_words = slice_cap / 4 + 64;
-    std::vector<KSeq> seqs((size_t)n * seq_cap);
-    std::vector<u8> lits((size_t)n * lit_cap, 0xEE);
-    std::vector<KSliceMeta> meta(n);
-    std::vector<u32> scratch((size_t)n * scratch_words, 0xA5A5A5A5u);
-    u32 const nteams = nblocks * (64 / G);
-    std::vector<u32> tables((size_t)nteams * KX_TBL_ENTRIES, 0xDEADBEEFu & 0x0003FFFFu);
-    std::vector<u32> epoch(nteams, 7);
+    if (!team_width_ok(G)) return -2;
+    Work w(n, slice_cap);
+    KBatchView const v = w.view(src, in_off, in_len, n, dst, out_off, out_len);
+    Teams teams(nblocks, G, 7);
     u32 counter = 0;
-    KFastArgs g;
-    g.m.src = src; g.m.in_off = in_off; g.m.in_len = in_len; g.m.n_slices = n;
-    g.m.seqs = seqs.data(); g.m.seq_cap = seq_cap; g.m.lits = lits.data(); g.m.lit_cap = lit_cap; g.m.meta = meta.data();
-    g.m.tables = tables.data(); g.m.team_epoch = epoch.data(); g.m.counter = &counter; g.m.flags = 6; g.m.fstate = nullptr; g.m.big_tables = nullptr;
-    g.level = level < 0 ? 0u : (u32)level; g.step0 = level < 0 ? (u32)(1 - level) : 2u;     // negative levels: row 0, a step of 1 - level
+    KFastArgs const g = kx_fast_args(v, teams.get(), &counter, level);
     kxemu::failed = 0;
-    switch (G) {
-    case 2:  kxemu::launch(nblocks, [&]() { zstd_match_fast_body<2>(g); }); break;
-    case 4:  kxemu::launch(nblocks, [&]() { zstd_match_fast_body<4>(g); }); break;
-    case 8:  kxemu::launch(nblocks, [&]() { zstd_match_fast_body<8>(g); }); break;
-    case 16: kxemu::launch(nblocks, [&]() { zstd_match_fast_body<16>(g); }); break;
-    default: return -2;
-    }
+    by_team_width(G, [&](auto tw) { kxemu::launch(nblocks, [&]() { zstd_match_fast_body<decltype(tw)::value>(g); }); });
     if (kxemu::failed) return -1;
-    for (u32 i = 0; i < n; i++) if (meta[i].status) return -3;
-    KEntropyArgs e;
-    e.src = src; e.in_off = in_off; e.in_len = in_len; e.n_slices = n;
-    e.seqs = seqs.data(); e.seq_cap = seq_cap; e.lits = lits.data(); e.lit_cap = lit_cap; e.meta = meta.data();
-    e.scratch = scratch.data(); e.scratch_words = scratch_words;
-    e.dst = dst; e.out_off = out_off; e.out_len = out_len; e.flags = 8u | 32u | (level < 0 ? 64u : 0u);
+    if (any_status(v.meta, n)) return -3;
+    KEntropyArgs const e = kx_entropy_args(v, kx_entropy_flags_fast(level < 0));
     kxemu::launch(nblocks, [&]() { zstd_entropy_body(e); });
     return kxemu::failed ? -1 : 0;
 }
 
-#include "zstd_match_dict.h"
 #include "zstd_cdict_host.h"
-// Compress with a raw-content dictionary: dictionary match kernel + entropy kernel on the emulator.
+// Compress with a dictionary (raw content, or zstd's format): the host code's steps of kmp_zstd_compress_batch_dict, the dictionary
+// match kernel + the entropy kernel on the emulator.
 extern "C" __attribute__((visibility("default")))
 int emu_zstd_compress_dict(const u8* src, const u64* in_off, const u32* in_len, u32 n, int G, u32 nblocks,
                            u8* dst, const u64* out_off, u32* out_len, u32 slice_cap, const u8* dict, u32 dict_size)
 {
-    u32 const seq_cap = (slice_cap / 4 + 8 + 15) & ~15u, lit_cap = slice_cap + 64, scratch_words = slice_cap / 4 + 64;
-    std::vector<KSeq> seqs((size_t)n * seq_cap);
-    std::vector<u8> lits((size_t)n * lit_cap, 0xEE);
-    std::vector<KSliceMeta> meta(n);
-    std::vector<u32> scratch((size_t)n * scratch_words, 0xA5A5A5A5u);
-    u32 const nteams = nblocks * (64 / G);
-    std::vector<u32> tables((size_t)nteams * KX_TBL_ENTRIES, 0xDEADBEEFu & 0x0003FFFFu);
-    std::vector<u32> epoch(nteams, 7);
+    if (!team_width_ok(G)) return -2;
+    Work w(n, slice_cap);
+    KBatchView const v = w.view(src, in_off, in_len, n, dst, out_off, out_len);
+    Teams teams(nblocks, G, 7);
     u32 counter = 0, W, C, H, M;
-    // (a formatted dictionary: the host code's steps of kmp_zstd_compress_batch_dict)
     KDictPrior prior; size_t content_off = 0;
     int const formatted = cdict_parse_formatted(dict, dict_size, &prior, &content_off);
     if (formatted < 0) return -4;
@@ -172,76 +155,42 @@ int emu_zstd_compress_dict(const u8* src, const u64* in_off, const u32* in_len, 
     dict += content_off; dict_size -= (u32)content_off;
     std::vector<u32> tl, ts;
     cdict_fill(tl, H, ts, C, M, dict, dict_size);
-    KDictArgs g;
-    if (formatted) { g.rep0 = prior.rep[0]; g.rep1 = prior.rep[1]; }
-    g.m.src = src; g.m.in_off = in_off; g.m.in_len = in_len; g.m.n_slices = n;
-    g.m.seqs = seqs.data(); g.m.seq_cap = seq_cap; g.m.lits = lits.data(); g.m.lit_cap = lit_cap; g.m.meta = meta.data();
-    g.m.tables = tables.data(); g.m.team_epoch = epoch.data(); g.m.counter = &counter; g.m.flags = 6; g.m.fstate = nullptr; g.m.big_tables = nullptr;
-    g.dict = dict; g.dict_size = dict_size; g.dictL = tl.data(); g.dictS = ts.data();
-    g.dWindowLog = W; g.dHashLog = H; g.dChainLog = C; g.dMinMatch = M;
+    KDictArgs const g = kx_dict_args(v, teams.get(), &counter, dict, dict_size, tl.data(), ts.data(), W, H, C, M, formatted ? prior.rep[0] : 1u, formatted ? prior.rep[1] : 4u);
     kxemu::failed = 0;
-    switch (G) {
-    case 2:  kxemu::launch(nblocks, [&]() { zstd_match_dict_body<2>(g); }); break;
-    case 4:  kxemu::launch(nblocks, [&]() { zstd_match_dict_body<4>(g); }); break;
-    case 8:  kxemu::launch(nblocks, [&]() { zstd_match_dict_body<8>(g); }); break;
-    case 16: kxemu::launch(nblocks, [&]() { zstd_match_dict_body<16>(g); }); break;
-    default: return -2;
-    }
+    by_team_width(G, [&](auto tw) { kxemu::launch(nblocks, [&]() { zstd_match_dict_body<decltype(tw)::value>(g); }); });
     if (kxemu::failed) return -1;
-    for (u32 i = 0; i < n; i++) if (meta[i].status) return -3;
-    KEntropyArgs e;
-    e.src = src; e.in_off = in_off; e.in_len = in_len; e.n_slices = n;
-    e.seqs = seqs.data(); e.seq_cap = seq_cap; e.lits = lits.data(); e.lit_cap = lit_cap; e.meta = meta.data();
-    e.scratch = scratch.data(); e.scratch_words = scratch_words;
-    e.dst = dst; e.out_off = out_off; e.out_len = out_len; e.flags = 8u;
-    if (formatted) { e.prior = &prior; kxemu::launch(nblocks, [&]() { zstd_entropy_body<true>(e); }); }
+    if (any_status(v.meta, n)) return -3;
+    KEntropyArgs const e = kx_entropy_args(v, KXE_GATHER_LITS, formatted ? &prior : nullptr);
+    if (formatted) kxemu::launch(nblocks, [&]() { zstd_entropy_body<true>(e); });
     else kxemu::launch(nblocks, [&]() { zstd_entropy_body(e); });
     return kxemu::failed ? -1 : 0;
 }
 
-#include "zstd_lazy.h"
 // Levels 5 .. 10 (greedy / lazy / lazy2): sort body (workgroups of four waves), parse body, entropy body -- zstd_compress_lazy's steps.
 extern "C" __attribute__((visibility("default")))
 int emu_zstd_compress_lazy(const u8* src, const u64* in_off, const u32* in_len, u32 n, u32 nblocks,
                            u8* dst, const u64* out_off, u32* out_len, u32 slice_cap, int level)
 {
-    u32 const seq_cap = (slice_cap / 4 + 8 + 15) & ~15u, lit_cap = slice_cap + 64, scratch_words = slice_cap / 4 + 64, pos_cap = (slice_cap + 63u) & ~63u;
-    std::vector<KSeq> seqs((size_t)n * seq_cap);
-    std::vector<u8> lits((size_t)n * lit_cap, 0xEE);
-    std::vector<KSliceMeta> meta(n);
-    std::vector<u32> scratch((size_t)n * scratch_words, 0xA5A5A5A5u);
-    std::vector<u32> wr((size_t)n * pos_cap, 0xCCCCCCCCu); std::vector<KLazyRec> rec((size_t)n * pos_cap);
+    Work w(n, slice_cap);
+    KBatchView const v = w.view(src, in_off, in_len, n, dst, out_off, out_len);
+    std::vector<u32> wr((size_t)n * w.cap.pos_cap, 0xCCCCCCCCu); std::vector<KLazyRec> rec((size_t)n * w.cap.pos_cap);
     memset(rec.data(), 0xBB, rec.size() * sizeof(KLazyRec));
-    for (u32 i = 0; i < n; i++) { memset(&meta[i], 0, sizeof(meta[i])); meta[i].lastLL = in_len[i]; meta[i].status = 3; }      // (level 4: what the double-fast kernel's slices look like to this harness: not served here)
-    KLazyArgs g;
-    g.src = src; g.in_off = in_off; g.in_len = in_len; g.n_slices = n;
-    g.rec = rec.data(); g.wr = wr.data(); g.pos_cap = pos_cap;
-    g.seqs = seqs.data(); g.seq_cap = seq_cap; g.meta = meta.data(); g.level = (u32)level;
+    for (u32 i = 0; i < n; i++) { memset(&w.meta[i], 0, sizeof(w.meta[i])); w.meta[i].lastLL = in_len[i]; w.meta[i].status = 3; }      // (level 4: what the double-fast kernel's slices look like to this harness: not served here)
+    KLazyArgs const g = kx_lazy_args(v, rec.data(), wr.data(), w.cap.pos_cap, level);
     kxemu::failed = 0;
     kxemu::launch_block(nblocks, 4, [&]() { zstd_lazy_sort_body(g); });
     if (kxemu::failed) return -1;
     if (slice_cap <= 65536u) kxemu::launch(nblocks, [&]() { zstd_lazy_body<2048>(g); }); else kxemu::launch(nblocks, [&]() { zstd_lazy_body<4096>(g); });
     if (kxemu::failed) return -2;
-    for (u32 i = 0; i < n; i++) if (meta[i].status == 2) return -3;
-    KEntropyArgs e;
-    e.src = src; e.in_off = in_off; e.in_len = in_len; e.n_slices = n;
-    e.seqs = seqs.data(); e.seq_cap = seq_cap; e.lits = lits.data(); e.lit_cap = lit_cap; e.meta = meta.data();
-    e.scratch = scratch.data(); e.scratch_words = scratch_words;
-    e.dst = dst; e.out_off = out_off; e.out_len = out_len; e.flags = 8u | ((u32)level << 12);
+    for (u32 i = 0; i < n; i++) if (w.meta[i].status == 2) return -3;
+    KEntropyArgs const e = kx_entropy_args(v, kx_entropy_flags_lazy(level));
     kxemu::launch(nblocks, [&]() { zstd_entropy_body(e); });
     if (kxemu::failed) return -4;
-    for (u32 i = 0; i < n; i++) if (meta[i].status == 3) out_len[i] = 0;          // (k_len_guard_finish: another strategy at this size)
+    for (u32 i = 0; i < n; i++) if (w.meta[i].status == 3) out_len[i] = 0;          // (k_len_guard_finish: another strategy at this size)
     return 0;
 }
 
-// Frames of several blocks (slices above 128 KiB): the host-side round loop of kmp_api.hip restated for the emulator.
-extern "C" __attribute__((visibility("default")))
-int emu_zstd_compress_big_ex(const u8* src, const u64* in_off, const u32* in_len, u32 n, int G, u32 nblocks,
-                             u8* dst, const u64* out_off, u32* out_len, u32* rounds_out, u32 stream);
-extern "C" __attribute__((visibility("default")))
-int emu_zstd_compress_big(const u8* src, const u64* in_off, const u32* in_len, u32 n, int G, u32 nblocks,
-                          u8* dst, const u64* out_off, u32* out_len, u32* rounds_out)
-{ return emu_zstd_compress_big_ex(src, in_off, in_len, n, G, nblocks, dst, out_off, out_len, rounds_out, 0); }
+// Frames of several blocks (slices above 128 KiB): zstd_compress_big's steps (kmp_batch.hip) on the emulator.
 extern "C" __attribute__((visibility("default")))
 int emu_zstd_compress_big_ex2(const u8* src, const u64* in_off, const u32* in_len, u32 n, int G, u32 nblocks,
                               u8* dst, const u64* out_off, u32* out_len, u32* rounds_out, u32 stream_and_strategy, u32 tail_or_chunk, u32 wide);
@@ -249,123 +198,74 @@ extern "C" __attribute__((visibility("default")))
 int emu_zstd_compress_big_ex(const u8* src, const u64* in_off, const u32* in_len, u32 n, int G, u32 nblocks,
                              u8* dst, const u64* out_off, u32* out_len, u32* rounds_out, u32 stream_and_strategy)
 { return emu_zstd_compress_big_ex2(src, in_off, in_len, n, G, nblocks, dst, out_off, out_len, rounds_out, stream_and_strategy, 0, 0); }
-// stream (low byte): KFrameArgs.stream, 0 .. 3; tail_or_chunk: tail_direct of a stream, out_chunk of the one-shot driver (mode 3);
-// wide: table entries without check bits (what contexts for slices of 4 MiB and more use)
+extern "C" __attribute__((visibility("default")))
+int emu_zstd_compress_big(const u8* src, const u64* in_off, const u32* in_len, u32 n, int G, u32 nblocks,
+                          u8* dst, const u64* out_off, u32* out_len, u32* rounds_out)
+{ return emu_zstd_compress_big_ex(src, in_off, in_len, n, G, nblocks, dst, out_off, out_len, rounds_out, 0); }
+// stream (low byte): KFrameArgs.stream; the next byte: zstd_compress_big's strategy (1: level 1, 2: level 2), or 4: level 4's double-fast rows
+// (the level-3 kernels, larger tables); bits 16 ..: a negative level's step (1 - level), with strategy 1.  tail_or_chunk: tail_direct of a
+// stream, out_chunk of the one-shot driver (KXF_REFERENCE); wide: table entries without check bits (what contexts for slices of 4 MiB and more use)
 extern "C" __attribute__((visibility("default")))
 int emu_zstd_compress_big_ex2(const u8* src, const u64* in_off, const u32* in_len, u32 n, int G, u32 nblocks,
                               u8* dst, const u64* out_off, u32* out_len, u32* rounds_out, u32 stream_and_strategy, u32 tail_or_chunk, u32 wide)
 {
-    u32 const stream = stream_and_strategy & 0xFFu; u32 strategy = (stream_and_strategy >> 8) & 0xFFu;     // strategy 1: level 1 (fast); 2: level 2 (as zstd_compress_big in kmp_api.hip)
-    bool const level4 = strategy == 4u; if (level4) strategy = 0;                                           // 4: level 4's double-fast rows (the level-3 kernels, larger tables)
-    u32 const fast_step0 = strategy == 1u ? stream_and_strategy >> 16 : 0u;                               // bits 16 ..: a negative level's step (1 - level), with strategy 1
-    u32 const level2 = strategy == 2u ? 1u : 0u;
-    bool const streaming = stream == 1 || stream == 2;
-    u32 const block_cap = 128u * 1024u;
-    u32 const seq_cap = (block_cap / 4 + 8 + 15) & ~15u, lit_cap = block_cap + 64, scratch_words = block_cap / 4 + 64;
-    std::vector<KSeq> seqs((size_t)n * seq_cap);
-    std::vector<u8> lits((size_t)n * lit_cap, 0xEE);
-    std::vector<KSliceMeta> meta(n);
-    std::vector<u32> scratch((size_t)n * scratch_words, 0xA5A5A5A5u);
+    if (!team_width_ok(G)) return -2;
+    u32 const stream = stream_and_strategy & 0xFFu, sbyte = (stream_and_strategy >> 8) & 0xFFu;
+    KBigLevel const b = { sbyte == 4u ? 0u : sbyte, sbyte == 1u ? stream_and_strategy >> 16 : 0u, sbyte == 4u };
+    bool const streaming = stream == KXF_STREAM || stream == KXF_STREAM_EMPTY_END;
+    Work w(n, 128u * 1024u);
+    KBatchView const v = w.view(src, in_off, in_len, n, dst, out_off, out_len);
     std::vector<KFrameState> fstate(n);
     std::vector<u32> hufct((size_t)n * 512, 0xDEADBEEFu);
-    std::vector<u32> big_tables((size_t)n * (level4 ? KX_BIG4_ENTRIES : KX_BIG_TBL_ENTRIES), 0u);
+    std::vector<u32> big_tables((size_t)n * (b.level4 ? KX_BIG4_ENTRIES : KX_BIG_TBL_ENTRIES), 0u);
     u32 remaining = 0, counter = 0;
-    for (u32 i = 0; i < n; i++) {
+    for (u32 i = 0; i < n; i++) {           // (k_zstd_frame_init)
         KFrameState s; memset(&s, 0, sizeof(s));
         s.blockSize = in_len[i] < KX_BLOCK_MAX ? in_len[i] : KX_BLOCK_MAX; s.first = 1; s.rep[0] = 1; s.rep[1] = 4; s.rep[2] = 8;
-        s.lowLimit = 2; s.dictLimit = 2; s.chunkEnd = (stream != 0 && in_len[i] > KX_BLOCK_MAX) ? KX_BLOCK_MAX : in_len[i];
-        if (level4 && !streaming && !kx_l4_served(in_len[i])) { s.blockSize = 0; s.chunkEnd = 0; fstate[i] = s; out_len[i] = 0; continue; }      // (k_zstd_frame_init: refused size class)
+        s.lowLimit = 2; s.dictLimit = 2; s.chunkEnd = (stream != KXF_ONE_SHOT && in_len[i] > KX_BLOCK_MAX) ? KX_BLOCK_MAX : in_len[i];
+        if (b.level4 && !streaming && !kx_l4_served(in_len[i])) { s.blockSize = 0; s.chunkEnd = 0; fstate[i] = s; out_len[i] = 0; continue; }      // (refused size class)
         fstate[i] = s;
-        if (in_len[i] == 0) { u8* d = dst + out_off[i]; u32 const magic = 0xFD2FB528u; memcpy(d, &magic, 4); d[4] = streaming ? 0x00 : 0x20; d[5] = streaming ? (strategy == 1u ? 0x48 : strategy == 2u ? 0x50 : 0x58) : 0; d[6] = 1; d[7] = 0; d[8] = 0; out_len[i] = 9; }
+        if (in_len[i] == 0) { u8* d = dst + out_off[i]; u32 const magic = 0xFD2FB528u, wd = kx_big_window_byte(stream, b.strategy); memcpy(d, &magic, 4); d[4] = wd ? 0x00 : 0x20; d[5] = (u8)wd; d[6] = 1; d[7] = 0; d[8] = 0; out_len[i] = 9; }
         else remaining++;
     }
-    KMatchArgs m;
-    m.src = src; m.in_off = in_off; m.in_len = in_len; m.n_slices = n;
-    m.seqs = seqs.data(); m.seq_cap = seq_cap; m.lits = lits.data(); m.lit_cap = lit_cap; m.meta = meta.data();
-    m.tables = nullptr; m.team_epoch = nullptr; m.counter = &counter; m.flags = (streaming ? 8u : 0u) | (wide ? 16u : 0u);
-    m.fstate = fstate.data(); m.big_tables = big_tables.data();
-    if (level4) { m.level = 4; m.big_stride = KX_BIG4_ENTRIES; m.big_long = KX_BIG4_LONG; }
-    KFrameArgs e;
-    e.src = src; e.in_off = in_off; e.in_len = in_len; e.n_slices = n;
-    e.seqs = seqs.data(); e.seq_cap = seq_cap; e.lits = lits.data(); e.lit_cap = lit_cap; e.meta = meta.data();
-    e.scratch = scratch.data(); e.scratch_words = scratch_words;
-    e.dst = dst; e.out_off = out_off; e.out_len = out_len;
-    e.fstate = fstate.data(); e.hufct = hufct.data(); e.remaining = &remaining; e.stream = stream; e.strategy = strategy ? 1u : 0u; e.level2 = level2; e.cls = 0; e.fast_step0 = fast_step0;
-    e.tail_direct = stream == 3 ? 0u : tail_or_chunk; e.out_chunk = stream == 3 ? tail_or_chunk : 0u;
-    if (strategy && rounds_out) return -6;
+    KMatchArgs const m = kx_match_args_blk(v, kx_one_piece(nullptr, nullptr), &counter, streaming, wide != 0, fstate.data(), big_tables.data(), b.level4);
+    KFrameArgs const e = kx_frame_args(v, fstate.data(), hufct.data(), &remaining, nullptr, stream, b, tail_or_chunk);
+    if (b.strategy && rounds_out) return -6;
     if (!rounds_out) {
         // product path: one wave per slice walks its chain of blocks
         std::vector<u32> counters(nblocks, 0u);
-        KBigArgs g; g.m = m; g.e = e; g.counters = counters.data(); g.spw = (n > 2 && 64 / G >= 2) ? 2 : 1;
+        KBigArgs g = kx_big_args(m, e, counters.data(), (n > 2 && 64 / G >= 2) ? 2 : 1);
         kxemu::failed = 0;
-        if (level2 && !streaming) {
-            // level 2, sizes known: the slices of its double-fast row first (class 1), the others (class 2) through the fast parser below
-            g.e.strategy = 0; g.e.cls = 1; g.m.flags = m.flags | 32u | (1u << 6);
-            switch (G) {
-            case 2:  kxemu::launch(nblocks, [&]() { zstd_big_body<2>(g); }); break;
-            case 4:  kxemu::launch(nblocks, [&]() { zstd_big_body<4>(g); }); break;
-            case 8:  kxemu::launch(nblocks, [&]() { zstd_big_body<8>(g); }); break;
-            case 16: kxemu::launch(nblocks, [&]() { zstd_big_body<16>(g); }); break;
-            case 32: kxemu::launch(nblocks, [&]() { zstd_big_body<32>(g); }); break;
-            case 64: kxemu::launch(nblocks, [&]() { zstd_big_body<64>(g); }); break;
-            default: return -2;
-            }
+        if (b.strategy == 2u && !streaming) {
+            // level 2, sizes known: the slices of its double-fast row first, the others through the fast parser below
+            kx_big_set_class(g, m.flags, KXC_L2_DFAST);
+            by_team_width(G, [&](auto tw) { kxemu::launch(nblocks, [&]() { zstd_big_body<decltype(tw)::value>(g); }); });
             if (kxemu::failed) return -1;
             for (auto& x : counters) x = 0;
-            g.e.strategy = 1; g.e.cls = 2; g.m.flags = m.flags | (2u << 6);
+            kx_big_set_class(g, m.flags, KXC_L2_FAST);
         }
-        if (strategy) switch (G) {
-        case 2:  kxemu::launch(nblocks, [&]() { zstd_big_body<2, true>(g); }); break;
-        case 4:  kxemu::launch(nblocks, [&]() { zstd_big_body<4, true>(g); }); break;
-        case 8:  kxemu::launch(nblocks, [&]() { zstd_big_body<8, true>(g); }); break;
-        case 16: kxemu::launch(nblocks, [&]() { zstd_big_body<16, true>(g); }); break;
-        case 32: kxemu::launch(nblocks, [&]() { zstd_big_body<32, true>(g); }); break;
-        case 64: kxemu::launch(nblocks, [&]() { zstd_big_body<64, true>(g); }); break;
-        default: return -2;
-        }
-        else switch (G) {
-        case 2:  kxemu::launch(nblocks, [&]() { zstd_big_body<2>(g); }); break;
-        case 4:  kxemu::launch(nblocks, [&]() { zstd_big_body<4>(g); }); break;
-        case 8:  kxemu::launch(nblocks, [&]() { zstd_big_body<8>(g); }); break;
-        case 16: kxemu::launch(nblocks, [&]() { zstd_big_body<16>(g); }); break;
-        case 32: kxemu::launch(nblocks, [&]() { zstd_big_body<32>(g); }); break;
-        case 64: kxemu::launch(nblocks, [&]() { zstd_big_body<64>(g); }); break;
-        default: return -2;
-        }
+        if (b.strategy) by_team_width(G, [&](auto tw) { kxemu::launch(nblocks, [&]() { zstd_big_body<decltype(tw)::value, true>(g); }); });
+        else by_team_width(G, [&](auto tw) { kxemu::launch(nblocks, [&]() { zstd_big_body<decltype(tw)::value>(g); }); });
         if (kxemu::failed) return -1;
         for (u32 i = 0; i < n; i++) if (fstate[i].blockSize != 0) return -5;
         return 0;
     }
+    // the block rounds as separate launches (the ablation build's KMP_BIG_ROUNDS=1)
     u32 rounds = 0;
     while (remaining != 0) {
         if (++rounds > 20000) return -4;
         counter = 0; kxemu::failed = 0;
-        switch (G) {
-        case 2:  kxemu::launch(nblocks, [&]() { zstd_match_body<2, true>(m); }); break;
-        case 4:  kxemu::launch(nblocks, [&]() { zstd_match_body<4, true>(m); }); break;
-        case 8:  kxemu::launch(nblocks, [&]() { zstd_match_body<8, true>(m); }); break;
-        case 16: kxemu::launch(nblocks, [&]() { zstd_match_body<16, true>(m); }); break;
-        case 32: kxemu::launch(nblocks, [&]() { zstd_match_body<32, true>(m); }); break;
-        case 64: kxemu::launch(nblocks, [&]() { zstd_match_body<64, true>(m); }); break;
-        default: return -2;
-        }
+        by_team_width(G, [&](auto tw) { kxemu::launch(nblocks, [&]() { zstd_match_body<decltype(tw)::value, true>(m); }); });
         if (kxemu::failed) return -1;
         // the blocks libzstd parses with the extDict variant (behind a wrap of its staging buffer)
         counter = 0;
-        switch (G) {
-        case 2:  kxemu::launch(nblocks, [&]() { zstd_match_ext_body<2>(m); }); break;
-        case 4:  kxemu::launch(nblocks, [&]() { zstd_match_ext_body<4>(m); }); break;
-        case 8:  kxemu::launch(nblocks, [&]() { zstd_match_ext_body<8>(m); }); break;
-        case 16: kxemu::launch(nblocks, [&]() { zstd_match_ext_body<16>(m); }); break;
-        case 32: kxemu::launch(nblocks, [&]() { zstd_match_ext_body<32>(m); }); break;
-        default: kxemu::launch(nblocks, [&]() { zstd_match_ext_body<64>(m); }); break;
-        }
+        by_team_width(G, [&](auto tw) { kxemu::launch(nblocks, [&]() { zstd_match_ext_body<decltype(tw)::value>(m); }); });
         if (kxemu::failed) return -1;
-        for (u32 i = 0; i < n; i++) if (fstate[i].blockSize >= 8 && meta[i].status) return -3;
+        for (u32 i = 0; i < n; i++) if (fstate[i].blockSize >= 8 && w.meta[i].status) return -3;
         kxemu::launch(nblocks, [&]() { zstd_frame_body(e); });
         if (kxemu::failed) return -1;
     }
-    if (rounds_out) *rounds_out = rounds;
+    *rounds_out = rounds;
     return 0;
 }
 
