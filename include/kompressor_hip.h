@@ -52,7 +52,7 @@ KMP_API kmp_zstd_cctx* kmp_zstd_create_cctx(void);
 KMP_API size_t kmp_zstd_free_cctx(kmp_zstd_cctx* cctx);
 /* replaces ZSTD_CCtx_setParameter     (Wrapper.cpp:29-39). Levels -131072 .. -1 and 1 .. 10 (0 = default = 3) run on the GPU where
  * kmp_zstd_compress_batch_level serves them (dictionaries: level 3 only; levels 5 .. 10: one closing call of at most 128 KiB -- 9 and 10
- * above 16 KiB; what is not served surfaces when the stream closes); levels 11 and up return (size_t)-40 "Unsupported parameter". */
+ * above 16 KiB --, or of up to 2 MiB when the call's output slice has room for kmp_zstd_compress_bound of it; what is not served surfaces when the stream closes); levels 11 and up return (size_t)-40 "Unsupported parameter". */
 KMP_API size_t kmp_zstd_cctx_set_parameter(kmp_zstd_cctx* cctx, int param, int value);
 /* replaces ZSTD_CCtx_loadDictionary   (Wrapper.cpp:41-56). Served: dictionaries of 8 .. 130 560 bytes for slices <= 128 KiB, raw content
  * or zstd's own format (magic EC30A437: what `zstd --train` / ZDICT_trainFromBuffer write -- its Huffman and FSE tables, repeat offsets
@@ -70,7 +70,9 @@ KMP_API size_t kmp_zstd_cctx_load_dictionary(kmp_zstd_cctx* cctx, const void* di
  * slices hold max(8192, n / 10) bytes -- the input is staged in chunks of 128 KiB (kmp_zstd_compress_batch_reference),
  * and data that arrived with e_continue makes it a streaming frame (no content size).  Input is collected until e_end;
  * streams up to 1 GiB at every served level (beyond a level's window -- 512 KiB at level 1 and the negative levels, 1 MiB
- * at level 2, 2 MiB at levels 3 and 4 -- the window slides as libzstd's does). */
+ * at level 2, 2 MiB at levels 3 and 4 -- the window slides as libzstd's does).
+ * Levels 5 .. 10 above 128 KiB: only the in-place case is served (e_end with nothing staged, room for kmp_zstd_compress_bound, 128 KiB + 1 ..
+ * 2 MiB, no dictionary); staged chunks, data that arrived with e_continue and a loaded dictionary return "Unsupported parameter". */
 KMP_API size_t kmp_zstd_compress_stream(kmp_zstd_cctx* cctx,
                                         void* dst, size_t dst_size, size_t* dst_pos,
                                         const void* src, size_t src_size, size_t* src_pos,
@@ -143,7 +145,7 @@ typedef struct kmp_batch_ctx kmp_batch_ctx;
  * slice gets d_out_len[i] = 0 (a frame or stream is never empty) and the context's status word collects these bits. */
 #define KMP_STATUS_SLICE_TOO_LARGE 1u   /* a d_in_len[i] above the context's max_slice_bytes (DEFLATE: above 64 KiB) */
 #define KMP_STATUS_KERNEL_GUARD    2u   /* a parser's loop guard tripped (never expected) */
-#define KMP_STATUS_LEVEL_SIZE      4u   /* the level is another strategy at a slice's size (level 4: 128 - 256 KiB; levels 9, 10: 8 bytes .. 16 KiB): out_len 0 */
+#define KMP_STATUS_LEVEL_SIZE      4u   /* the level is not served at a slice's size (level 4: 128 - 256 KiB; levels 9, 10: 8 bytes .. 16 KiB; levels 5 .. 10: above 2 MiB): out_len 0 */
 
 #define KMP_MAX_SLICE_BYTES (128u * 1024u)        /* one block per frame: the batched fast path */
 #define KMP_MAX_BIG_SLICE_BYTES (1u << 30)       /* frames of several blocks (context created with max_slice_bytes above
@@ -255,9 +257,16 @@ KMP_API int kmp_zstd_compress_batch_reference(kmp_batch_ctx* ctx,
  * KMP_STATUS_LEVEL_SIZE).
  * Levels 5 .. 10 are libzstd's strategies "greedy" (5; 4 up to 16 KiB), "lazy" (6; 5 up to 16 KiB) and "lazy2" (7 .. 10; 6 .. 8 up to
  * 16 KiB) over its row-based match finder (windows above 2^14: the finder a library built for 128-bit vectors uses, as the reference's JNI
- * library is) or its hash chains (slices up to 16 KiB): served for slices of one block (<= 128 KiB, context created for such slices).  At
+ * library is) or its hash chains (slices up to 16 KiB): served for slices of one block (<= 128 KiB) and, on a context created
+ * for slices above 128 KiB, as frames of several blocks for slices of 128 KiB + 1 .. 2 MiB: the frames ZSTD_compress2 writes into a buffer
+ * of ZSTD_compressBound bytes (row tables, repeat offsets and entropy tables carried from block to block, the strategies' pre-splitter).  On
+ * such a context the slices of a batch up to 128 KiB come out as on the one-block path; a slice above 2 MiB is refused per slice (out_len 0,
+ * KMP_STATUS_LEVEL_SIZE: libzstd's parameters are pinned up to there), the rest of the batch is compressed.  At
  * levels 9 and 10 a slice of 8 bytes .. 16 KiB is strategy "btlazy2": refused as above.  The first batch at these levels allocates their
- * workspace (16 bytes per position of up to 16 384 slices). */
+ * workspace (16 bytes per position of up to 16 384 slices; on a context for larger slices also libzstd's own row tables, 5 bytes << hashLog
+ * -- 2.5 MiB a slice up to 256 KiB, 20 MiB at 2 MiB -- for the slices in flight: what 8 GiB hold, 4 096 at most, KMP_LAZY_BIG_SLICES caps
+ * it; a larger batch goes through in pieces).  Not served at these levels: streams, kmp_zstd_compress_batch_reference's staged frames,
+ * dictionaries. */
 KMP_API int kmp_zstd_compress_batch_level(kmp_batch_ctx* ctx,
                                           const void* d_src, const uint64_t* d_in_off, const uint32_t* d_in_len,
                                           uint32_t n,

@@ -172,8 +172,9 @@ class ZstdBatch:
         dictionary shared by all slices (host memory; raw content, or zstd's own format -- magic EC30A437 -- with its tables,
         repeat offsets and ID; level 3, slices up to 128 KiB; its tables are built once per dictionary).
         level: 3 (default); 1 / 2 / a negative level at any size the context holds (without a dictionary); 4 up to 128 KiB and above
-        256 KiB; 5 .. 10 (libzstd's greedy / lazy / lazy2 parsers) for slices up to 128 KiB -- at 9 and 10 a slice of 8 bytes .. 16 KiB is
-        another strategy and comes back refused (out_len 0, status bit 4), as does a level-4 slice between 128 and 256 KiB.
+        256 KiB; 5 .. 10 (libzstd's greedy / lazy / lazy2 parsers) for slices up to 128 KiB and, on a context created for larger slices, up to
+        2 MiB (frames of several blocks, as ZSTD_compress2 writes them) -- at 9 and 10 a slice of 8 bytes .. 16 KiB is another strategy and
+        comes back refused (out_len 0, status bit 4), as do a slice above 2 MiB at levels 5 .. 10 and a level-4 slice between 128 and 256 KiB.
         streaming: None = one-shot frames; "data" / "empty" = the frames of slices that arrived through finish = false
         calls, closed by a call with / without data (context created for slices above 128 KiB; levels 1 to 3).
         reference: the frames ZstdCompressor(level).transform(bytes) returns -- above 128 KiB the reference's output slices

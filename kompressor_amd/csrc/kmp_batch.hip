@@ -31,6 +31,25 @@ __global__ __launch_bounds__(64, 4) void k_zstd_entropy(KEntropyArgs a) { zstd_e
 // zstd levels 5 .. 10 (greedy / lazy / lazy2: zstd_lazy.h)
 __global__ __launch_bounds__(256) void k_zstd_lazy_sort(KLazyArgs a) { zstd_lazy_sort_body(a); }
 template <int WORDS> __global__ __launch_bounds__(64, 2) void k_zstd_lazy(KLazyArgs a) { zstd_lazy_body<WORDS>(a); }
+// ... above 128 KiB, up to 2 MiB: frames of several blocks, a wave walks a slice's chain of parse and frame step (zstd_lazy_big.h)
+__global__ __launch_bounds__(64, 2) void k_zstd_lazy_big(KLazyBigArgs a) { zstd_lazy_big_body(a); }
+// the lengths the one-block kernels of such a batch see: a slice above 128 KiB reads as empty there (its frame comes from k_zstd_lazy_big)
+__global__ __launch_bounds__(256) void k_zstd_lazy_small_len(const u32* in_len, u32 n, u32* small_len)
+{
+    u32 const i = blockIdx.x * 256u + threadIdx.x;
+    if (i < n) { u32 const len = in_len[i]; small_len[i] = len > KX_BLOCK_MAX ? 0u : len; }
+}
+// k_zstd_frame_init's sibling: the frame states of the slices k_zstd_lazy_big takes; a slice above 2 MiB is refused (out_len 0, the status bit)
+__global__ __launch_bounds__(256) void k_zstd_lazy_big_init(const u32* in_len, u32 n, KFrameState* fs, KSeqPrev* prev, u32* out_len, u32* remaining, u32* status)
+{
+    u32 const i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    KFrameState s; bool refused;
+    zstd_lazy_big_init_slice(in_len[i], s, prev[i], refused);
+    fs[i] = s;
+    if (refused) { out_len[i] = 0; atomicOr(status, (u32)KMP_STATUS_LEVEL_SIZE); }
+    else if (s.blockSize) atomicAdd(remaining, 1u);
+}
 // ... of a batch parsed against a formatted dictionary: its tables as the block's predecessor, its ID in the frame header
 __global__ __launch_bounds__(64, 4) void k_zstd_entropy_prior(KEntropyArgs a) { zstd_entropy_body<true>(a); }
 #ifdef KMP_ABLATIONS
@@ -214,7 +233,7 @@ __global__ __launch_bounds__(64) void k_table_probe(u32* p0, u32* p1, u32* p2, u
     }
     if (acc == 0x12345678u) sink[0] = acc;
 }
-extern "C" const char* kmp_version(void) { return "kompressor_hip 0.4 (gfx950; zstd levels -131072 .. -1 and 1 .. 3: frames and streams up to 1 GiB, dictionaries (raw content and zstd format); level 4 up to 128 KiB, above 256 KiB and streams; levels 5 .. 10 up to 128 KiB; deflate / zlib / gzip levels 1-9, windowBits 9-15, memLevel 1-9; zstd and inflate decoders)"; }
+extern "C" const char* kmp_version(void) { return "kompressor_hip 0.4 (gfx950; zstd levels -131072 .. -1 and 1 .. 3: frames and streams up to 1 GiB, dictionaries (raw content and zstd format); level 4 up to 128 KiB, above 256 KiB and streams; levels 5 .. 10 up to 2 MiB (frames, not streams); deflate / zlib / gzip levels 1-9, windowBits 9-15, memLevel 1-9; zstd and inflate decoders)"; }
 
 u32 env_u32(const char* name, u32 dflt)
 {
@@ -516,7 +535,7 @@ extern "C" int kmp_batch_memory(kmp_batch_ctx* c, kmp_batch_memory_info* info)
     if (c->arena) m.arena_used = (size_t)c->nteams * KX_TBL_ENTRIES * sizeof(u32) + ns * c->seq_cap * sizeof(KSeq) + ns * c->lit_cap + ns * sizeof(KSliceMeta) + ns * c->scratch_words * sizeof(u32);
     m.workspace = c->seqs_buf.bytes + c->lits_buf.bytes + c->meta_buf.bytes + c->scratch_buf.bytes + c->tables_buf.bytes
                 + c->team_epoch.bytes + c->counter.bytes + c->len_ok.bytes + c->d_status.bytes;
-    m.other_tables = part_bytes(c->flat) + part_bytes(c->t4) + part_bytes(c->chain_t4) + part_bytes(c->dict) + part_bytes(c->ddict) + part_bytes(c->lz);
+    m.other_tables = part_bytes(c->flat) + part_bytes(c->t4) + part_bytes(c->chain_t4) + part_bytes(c->dict) + part_bytes(c->ddict) + part_bytes(c->lz) + part_bytes(c->lzb);
     m.block_chain = c->fstate.bytes + c->hufct.bytes + c->big_tables.bytes + c->remaining.bytes + c->big_counters.bytes;
     m.decode_staging = part_bytes(c->pre_seq) + part_bytes(c->pre_lit);
     m.deflate_workspace = part_bytes(c->dfl) + part_bytes(c->dflf);
@@ -582,7 +601,7 @@ extern "C" int kmp_batch_status(kmp_batch_ctx* c, uint32_t* bits, void* hip_stre
     if (bits) *bits = v;
     if (v & KMP_STATUS_SLICE_TOO_LARGE) { g_last_error = "a slice is larger than the context was created for: its out_len is 0"; return KMP_ERR_CAPACITY; }
     if (v & KMP_STATUS_KERNEL_GUARD) { g_last_error = "a parser's loop guard tripped: the slice's out_len is 0"; return KMP_ERR_KERNEL; }
-    if (v & KMP_STATUS_LEVEL_SIZE) { g_last_error = "the level is another strategy at a slice's size (levels 9 and 10 up to 16 KiB; level 4 between 128 and 256 KiB): that slice's out_len is 0"; return KMP_ERR_CAPACITY; }
+    if (v & KMP_STATUS_LEVEL_SIZE) { g_last_error = "the level is not served at a slice's size (levels 9 and 10 up to 16 KiB; level 4 between 128 and 256 KiB; levels 5 .. 10 above 2 MiB): that slice's out_len is 0"; return KMP_ERR_CAPACITY; }
     return KMP_OK;
 }
 
@@ -651,14 +670,16 @@ static int zstd_compress_dfast(kmp_batch_ctx* c, const void* d_src, const uint64
 // position stands): sort, then the wave-per-slice parse; the entropy kernel runs once over the whole batch.
 static int lazy_workspace(kmp_batch_ctx* c, u32 need_bytes);
 static int lazy_parse(kmp_batch_ctx* c, hipStream_t st, KBatchView const& v, int level);
+static int zstd_compress_lazy_big(kmp_batch_ctx* c, const void* d_src, const uint64_t* d_in_off, const uint32_t* d_in_len,
+                                  uint32_t n, void* d_dst, const uint64_t* d_out_off, uint32_t* d_out_len, hipStream_t st, int level);
 static int zstd_compress_lazy(kmp_batch_ctx* c, const void* d_src, const uint64_t* d_in_off, const uint32_t* d_in_len,
                               uint32_t n, void* d_dst, const uint64_t* d_out_off, uint32_t* d_out_len, void* hip_stream, int level)
 {
     KMP_TRY(batch_args("kmp_zstd_compress_batch_level", c, n, { d_src, d_in_off, d_in_len, d_dst, d_out_off, d_out_len }));
-    if (c->big) { g_last_error = "kmp_zstd_compress_batch_level: levels 5 .. 10 are served for slices up to 128 KiB"; return KMP_ERR_CAPACITY; }
     if (n == 0) return KMP_OK;
     hipStream_t const st = (hipStream_t)hip_stream;
     HIP_TRY(hipSetDevice(c->device));
+    if (c->big) return zstd_compress_lazy_big(c, d_src, d_in_off, d_in_len, n, d_dst, d_out_off, d_out_len, st, level);
     KMP_TRY(batch_begin(c, st, d_in_len, n, c->max_slice_bytes));          // (first: waits for the context's previous batch, whose workspace this may replace)
     KMP_TRY(lazy_workspace(c, c->max_slice_bytes));
     KBatchView const v = batch_view(c, d_src, d_in_off, n, d_dst, d_out_off, d_out_len);
@@ -704,6 +725,61 @@ static int lazy_parse(kmp_batch_ctx* c, hipStream_t st, KBatchView const& v, int
         HIP_TRY(hipGetLastError());
     }
     return KMP_OK;
+}
+
+// ... on a context for slices above 128 KiB.  The slices up to 128 KiB go through the one-block kernels above, which see every larger slice
+// as an empty one; then k_zstd_lazy_big walks the chains of the slices of 128 KiB + 1 .. 2 MiB, in pieces of as many slices as the part
+// holds table slots for.  A slice above 2 MiB is refused (libzstd's parameters are pinned up to there): out_len 0, KMP_STATUS_LEVEL_SIZE.
+static int lazy_big_workspace(kmp_batch_ctx* c)
+{
+    if (c->lzb) return KMP_OK;
+    auto fill = [c](lazy_big_part& z) {
+        z.slot_bytes = kx_lazy_big_slot_bytes(kx_lazy_big_hash_log_max(c->max_slice_bytes));
+        // slices in flight: what 8 GiB of tables hold, 4 096 at most (twice what the device runs at once); KMP_LAZY_BIG_SLICES caps it (the
+        // tests run a handful of slices through fewer slots)
+        u64 fit = ((u64)8 << 30) / z.slot_bytes; if (fit > 4096u) fit = 4096u;
+        u32 const cap = env_u32("KMP_LAZY_BIG_SLICES", (u32)fit);
+        if (cap && fit > cap) fit = cap;
+        if (fit > c->max_slices) fit = c->max_slices;
+        if (fit < 1u) fit = 1u;
+        z.chunk = (u32)fit;
+        KMP_TRY(z.tables.alloc((size_t)z.chunk * z.slot_bytes, "kmp_zstd_compress_batch_level: no memory for the row tables of levels 5 .. 10"));
+        KMP_TRY(z.prev.alloc((size_t)z.chunk * sizeof(KSeqPrev), "kmp_zstd_compress_batch_level: no memory for the workspace of levels 5 .. 10"));
+        KMP_TRY(z.small_len.alloc((size_t)c->max_slices * sizeof(u32), "kmp_zstd_compress_batch_level: no memory for the workspace of levels 5 .. 10"));
+        return KMP_OK;
+    };
+    return build_part(c->lzb, KMP_PART_LAZY_BIG, fill);
+}
+static int zstd_compress_lazy_big(kmp_batch_ctx* c, const void* d_src, const uint64_t* d_in_off, const uint32_t* d_in_len,
+                                  uint32_t n, void* d_dst, const uint64_t* d_out_off, uint32_t* d_out_len, hipStream_t st, int level)
+{
+    KMP_TRY(batch_begin(c, st, d_in_len, n, c->max_slice_bytes));
+    KMP_TRY(lazy_big_workspace(c));
+    KMP_TRY(lazy_workspace(c, KMP_MAX_SLICE_BYTES));
+    lazy_big_part const& z = *c->lzb;
+    KBatchView const v = batch_view(c, d_src, d_in_off, n, d_dst, d_out_off, d_out_len);
+    // the one-block slices (the others: empty frames there, replaced below)
+    hipLaunchKernelGGL(k_zstd_lazy_small_len, dim3((n + 255) / 256), dim3(256), 0, st, v.in_len, n, z.small_len.p);
+    HIP_TRY(hipGetLastError());
+    KBatchView sv = v; sv.in_len = z.small_len;
+    KMP_TRY(lazy_parse(c, st, sv, level));
+    KEntropyArgs const e = kx_entropy_args(sv, kx_entropy_flags_lazy(level));
+    hipLaunchKernelGGL(k_zstd_entropy, dim3(n), dim3(64), 0, st, e);
+    HIP_TRY(hipGetLastError());
+    // the frames of several blocks
+    HIP_TRY(hipMemsetAsync(c->remaining, 0, 4, st));
+    for (u32 first = 0; first < n; first += z.chunk) {
+        u32 const m = (n - first < z.chunk) ? n - first : z.chunk;
+        KBatchView const pv = v.sub(first, m);
+        hipLaunchKernelGGL(k_zstd_lazy_big_init, dim3((m + 255) / 256), dim3(256), 0, st, pv.in_len, m, c->fstate + first, z.prev.p, pv.out_len, c->remaining.p, c->d_status.p);
+        KLazyBigArgs const g = kx_lazy_big_args(pv, c->fstate + first, c->hufct + (size_t)first * 512u, c->remaining, c->d_status, z.tables, z.slot_bytes, z.prev, level);
+        hipLaunchKernelGGL(k_zstd_lazy_big, dim3(m), dim3(64), 0, st, g);
+        HIP_TRY(hipGetLastError());
+    }
+    c->last_rounds = 0; c->last_chunks = 1; c->zstd_timed = 0;
+    // (the per-slice records: of the one-block slices what their parser left -- "not served" at levels 9 and 10 up to 16 KiB --, of the others
+    // their last block's)
+    return batch_end(c, st, d_in_len, n, c->max_slice_bytes, d_out_len, c->meta);
 }
 
 extern "C" int kmp_zstd_compress_batch_level(kmp_batch_ctx* c, const void* d_src, const uint64_t* d_in_off, const uint32_t* d_in_len,

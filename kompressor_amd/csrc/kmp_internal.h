@@ -25,7 +25,7 @@ typedef uint32_t u32;
 typedef uint64_t u64;
 
 struct KSeq; struct KSliceMeta; struct KFrameState; struct KdBest; struct KdSliceMeta; struct KdBlockInfo; struct KPreBlk; struct KPreLit;
-struct KDictPrior; struct KDictDPrior;
+struct KDictPrior; struct KDictDPrior; struct KSeqPrev;
 
 // --------------------------------------------------------------------------
 // errors
@@ -96,7 +96,7 @@ using hip_stream = kmp_handle<hipStream_t, hipStreamCreateWithFlags, hipStreamDe
 // allocated is freed.  The ablation build's KMP_TEST_FAIL_PART=<code> fails the named part once fill has succeeded: what a
 // failing last allocation would leave (the earlier ones made, then freed), without a switch in the owners.
 enum { KMP_PART_DEFLATE_LAZY = 1, KMP_PART_DEFLATE_FAST, KMP_PART_LAZY_LEVELS, KMP_PART_DICT, KMP_PART_FLAT_TABLES, KMP_PART_TABLES4,
-       KMP_PART_CHAIN_TABLES4, KMP_PART_DDICT, KMP_PART_PRE_SEQ, KMP_PART_PRE_LIT };
+       KMP_PART_CHAIN_TABLES4, KMP_PART_DDICT, KMP_PART_PRE_SEQ, KMP_PART_PRE_LIT, KMP_PART_LAZY_BIG };
 template <class P, class F> int build_part(std::unique_ptr<P>& slot, u32 code, F const& fill)
 {
     std::unique_ptr<P> p(new (std::nothrow) P());
@@ -117,6 +117,12 @@ template <class P> size_t part_bytes(std::unique_ptr<P> const& p) { return p ? p
 struct table_part { dev_buf<u32> tables, epochs; u32 teams = 0; size_t bytes() const { return tables.bytes + epochs.bytes; } };
 // zstd levels 5 .. 10 (and level 4 up to 16 KiB): the sorted positions (KLazyRec), where each stands, the parse order (optional)
 struct lazy_part { dev_buf<u32> srt, wr, order; u32 pos_cap = 0, chunk = 0; size_t bytes() const { return srt.bytes + wr.bytes + order.bytes; } };
+// zstd levels 5 .. 10 over frames of several blocks (zstd_lazy_big.h): libzstd's row table and tags for `chunk` slices in flight (slot_bytes
+// each), their previous sequence tables; for the whole batch: the lengths the one-block kernels see (a larger slice reads as empty there)
+struct lazy_big_part {
+    dev_buf<u8> tables; dev_buf<KSeqPrev> prev; dev_buf<u32> small_len; u32 chunk = 0; u64 slot_bytes = 0;
+    size_t bytes() const { return tables.bytes + prev.bytes + small_len.bytes; }
+};
 // the dictionary of the last kmp_zstd_compress_batch_dict call: content, CDict tables (built on the host), a formatted one's tables
 struct dict_part {
     dev_buf<u8> content; dev_buf<u32> L, S; dev_buf<KDictPrior> prior;
@@ -179,6 +185,7 @@ struct kmp_batch_ctx {
     // the parts added on first use (null: absent)
     std::unique_ptr<table_part> flat, t4, chain_t4;
     std::unique_ptr<lazy_part> lz;
+    std::unique_ptr<lazy_big_part> lzb;
     std::unique_ptr<dict_part> dict;
     std::unique_ptr<ddict_part> ddict;
     std::unique_ptr<pre_seq_part> pre_seq; std::unique_ptr<pre_lit_part> pre_lit;

@@ -11,6 +11,7 @@
 #define KX_BLOCK_MAX (128u * 1024u)
 #define KX_MAX_DICT (128u * 1024u - 512u)
 #define KD_MAX_SLICE (1u << 30)
+#define KX_LAZY_BIG_MAX (2u << 20)
 
 #include "kmp_coalesce.h"
 
@@ -146,8 +147,10 @@ static size_t run_single_compress(kmp_zstd_cctx* c, size_t first_room, size_t en
     if (streaming && !c->dict.empty()) return KERRC(ZE_parameter_unsupported);
     // level 4: what arrives in one closing call, up to 128 KiB (its greedy and double-fast rows) or above 256 KiB; the rest: CPU library
     if (c->level == 4 && (!c->dict.empty() || (!streaming && !(n <= 131072u || n > 262144u)))) return KERRC(ZE_parameter_unsupported);
-    // levels 5 .. 10 (greedy / lazy / lazy2): one closing call of at most 128 KiB; 9 and 10 up to 16 KiB are "btlazy2": CPU library
-    if (c->level >= 5 && (!c->dict.empty() || streaming || n > KMP_MAX_SLICE_BYTES || (c->level >= 9 && n <= 16384u))) return KERRC(ZE_parameter_unsupported);
+    // levels 5 .. 10 (greedy / lazy / lazy2): one closing call of at most 128 KiB, or of up to 2 MiB that libzstd compresses in place (the
+    // frames of several blocks of zstd_lazy_big.h are ZSTD_compress2's; staged input cuts its blocks elsewhere); 9 and 10 up to 16 KiB are
+    // "btlazy2": CPU library
+    if (c->level >= 5 && (!c->dict.empty() || streaming || (n > KMP_MAX_SLICE_BYTES && (!in_place || n > KX_LAZY_BIG_MAX)) || (c->level >= 9 && n <= 16384u))) return KERRC(ZE_parameter_unsupported);
     if (c->level < 0 && !c->dict.empty()) return KERRC(ZE_parameter_unsupported);
     // the plain case -- level 3, no dictionary, the whole slice at once, one block -- joins whatever other contexts are
     // closing right now: one batch for all of them (kmp_coalesce.h); the frame is the one this context would get alone

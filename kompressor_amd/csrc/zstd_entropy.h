@@ -662,7 +662,7 @@ struct KHufPrev { const u32* ct; bool valid; u32* newCt; u32 outcome; bool compl
 
 // literals section at `dst`; returns its size (uniform across the wave)
 KX_DEV u32 kzstd_literals(KEntropyLds& lds, u8* dst, const u8* lits, u32 litSize, bool suspect, u32* scratch, int lane,
-                          KHufPrev* prev = nullptr, bool disabled = false)
+                          KHufPrev* prev = nullptr, bool disabled = false, bool preferRepeat = true)
 {
     u32 const lhSize = 3 + (litSize >= 1024) + (litSize >= 16384);
     bool const complete = prev && prev->valid && prev->complete;
@@ -702,7 +702,7 @@ KX_DEV u32 kzstd_literals(KEntropyLds& lds, u8* dst, const u8* lits, u32 litSize
                     // HUF_validateCTable: the old table must code every symbol present
                     bool repeat = prev && prev->valid;
                     if (repeat && !prev->complete) for (u32 sy = 0; sy <= maxSymbolValue; sy++) if (lds.hist[sy] != 0 && (prev->ct[sy] >> 16) == 0) { repeat = false; break; }
-                    if (repeat && litSize <= 1024) useOld = 1;          // HUF_flags_preferRepeat (strategy < lazy)
+                    if (repeat && preferRepeat && litSize <= 1024) useOld = 1;          // HUF_flags_preferRepeat (strategy < lazy; the caller says)
                     else {
                         u32 huffLog = kfse_optimal_tablelog(11, litSize, maxSymbolValue, 1);
                         huffLog = khuf_build_ctable(lds, maxSymbolValue, huffLog);
@@ -844,8 +844,38 @@ KX_DEV u32 kx_cross_entropy_cost(const short* dnorm, u32 accuracyLog, const u32*
 }
 
 #define KSET_REPEAT 3u
+// The three sequence tables of the previous compressed block of a frame, as normalised counts (ZSTD_fseCTables_t with its repeat modes: what
+// the frames of several blocks at levels 5 .. 10 carry from block to block).  mode: 0 none (the block used the default table or a run-length
+// one), 1 a table built for an earlier block (FSE_repeat_check): from strategy "lazy" on, using it again is priced against the other choices.
+struct KSeqPrev { u32 mode[3], maxSym[3], log[3]; short norm[3][64]; };       // [0] LL, [1] OF, [2] ML
+// what kzstd_sequences chose for a block (wave-uniform), for the frame step to carry forward
+struct KSeqChoice { u32 type[3], maxSym[3], log[3]; };
+// ZSTD_fseBitCost: the block's codes priced with a previous table.  deltaNbBits of a symbol follows from its count and the table log
+// (kfse_build_ctable), so the counts are all that has to be kept.
+KX_DEV u32 kx_fse_bit_cost(const KSeqPrev& pv, int t, const u32* count, u32 max)
+{
+    u32 const tableLog = pv.log[t], tableSize = 1u << tableLog, badCost = (tableLog + 1u) << 8;
+    if (pv.maxSym[t] < max) return 0xFFFFFFFFu;
+    u32 cost = 0;
+    for (u32 s = 0; s <= max; s++) {
+        if (count[s] == 0) continue;
+        int const nc = pv.norm[t][s];
+        u32 dnb;
+        if (nc == 0) dnb = ((tableLog + 1u) << 16) - tableSize;
+        else if (nc == -1 || nc == 1) dnb = (tableLog << 16) - tableSize;
+        else { u32 const maxBitsOut = tableLog - kx_hb32((u32)nc - 1u); dnb = (maxBitsOut << 16) - ((u32)nc << maxBitsOut); }
+        u32 const minNbBits = dnb >> 16, threshold = (minNbBits + 1u) << 16;
+        u32 const deltaFromThreshold = threshold - (dnb + tableSize);
+        u32 const bitCost = ((minNbBits + 1u) << 8) - ((deltaFromThreshold << 8) >> tableLog);
+        if (bitCost >= badCost) return 0xFFFFFFFFu;
+        cost += count[s] * bitCost;
+    }
+    return cost >> 8;
+}
+// LAZY: a block of a frame of several blocks at levels 5 .. 10 (prev: the slice's KSeqPrev; maxOut: the largest code present)
+template <bool LAZY = false>
 KX_DEV u32 kx_build_seq_table(KEntropyLds& lds, int t, u32* count, u32 nbSeq, u32 lastCode, u32 firstCode,
-                              u32& typeOut, KFseCT& ct, u32 strat, const KDictPrior* prior = nullptr)
+                              u32& typeOut, KFseCT& ct, u32 strat, const KDictPrior* prior = nullptr, const KSeqPrev* prev = nullptr, u32* maxOut = nullptr)
 {
     u32 const mult = 10u - strat;             // (ZSTD_fast 1, ZSTD_dfast 2, ZSTD_greedy 3; from ZSTD_lazy = 4 on the choice is by price)
     static const short LL_defaultNorm[36] = { 4,3,2,2,2,2,2,2, 2,2,2,2,2,1,1,1, 2,2,2,2,2,2,2,2, 2,3,2,1,1,1,1,1, -1,-1,-1,-1 };
@@ -871,14 +901,28 @@ KX_DEV u32 kx_build_seq_table(KEntropyLds& lds, int t, u32* count, u32 nbSeq, u3
         type = KSET_COMPRESSED;
         if (kfse_normalize(norm, tl, count, nbSeq, max, nbSeq >= 2048) != KXE_ERR) {
             u32 const nc = kfse_write_ncount(op, norm, max, tl);
+            if (LAZY && prev && prev->mode[t]) {
+                // ... and the previous block's table as the third candidate
+                u32 const repeatCost = kx_fse_bit_cost(*prev, t, count, max);
+                u32 const compressedCost = nc == KXE_ERR ? 0xFFFFFFFFu : (nc << 3) + kx_entropy_cost(count, max, nbSeq);
+                if (basicCost <= repeatCost && basicCost <= compressedCost) type = KSET_BASIC;
+                else if (repeatCost <= compressedCost) type = KSET_REPEAT;
+            } else
             if (nc != KXE_ERR && basicCost <= (nc << 3) + kx_entropy_cost(count, max, nbSeq)) type = KSET_BASIC;
         }
     }
+    if (LAZY && maxOut) *maxOut = max;
     // ZSTD_selectEncodingType below strategy "lazy": a table that is valid as it stands (only a dictionary's can be) is reused for fewer than
     // 1 000 sequences, unless one code makes up the whole block or the default table is not allowed
     if (prior && prior->seqValid[t] && mostFrequent != nbSeq && defaultAllowed && nbSeq < 1000u) type = KSET_REPEAT;
     typeOut = type;
     ct.state = kxe_state(lds, t); ct.dnb = lds.u.seq.dnb[t]; ct.dfs = lds.u.seq.dfs[t]; ct.tableLog = 0;
+    if (LAZY && type == KSET_REPEAT) {
+        u32 const pm = prev->maxSym[t];
+        for (u32 s = 0; s <= pm; s++) norm[s] = prev->norm[t][s];
+        kfse_build_ctable(ct, norm, pm, prev->log[t], lds.cumul[t], kxe_tsym(lds, t));
+        return 0;
+    }
     if (type == KSET_REPEAT) {
         u32 const pm = prior->maxSym[t];
         for (u32 s = 0; s <= pm; s++) norm[s] = prior->norm[t][s];
@@ -916,7 +960,9 @@ KX_DEV void kx_cbuf_put(u32* cbuf, u32 pos, u32 v, u32 n)
 // sequences section at dst; returns size, 0 => "emit a raw block instead"
 // `cap`: bytes the section may take before the block is certain to be emitted raw (block size minus the literals
 // section): the writer stops there, so a pathological block can never run past the slice's output room.
-KX_DEV u32 kzstd_sequences(KEntropyLds& lds, u8* dst, const KSeq* seqs, u32 nbSeq, u32 longType, u32 longPos, int lane, u32 cap, u32 xflags = 0, const KDictPrior* prior = nullptr)
+template <bool LAZY = false>
+KX_DEV u32 kzstd_sequences(KEntropyLds& lds, u8* dst, const KSeq* seqs, u32 nbSeq, u32 longType, u32 longPos, int lane, u32 cap, u32 xflags = 0, const KDictPrior* prior = nullptr,
+                           const KSeqPrev* prev = nullptr, KSeqChoice* choice = nullptr)
 {
     u32 hdr = 0;
     if (lane == 0) {
@@ -936,14 +982,14 @@ KX_DEV u32 kzstd_sequences(KEntropyLds& lds, u8* dst, const KSeq* seqs, u32 nbSe
     kx_sync();
     // the three tables, one lane each
     KFseCT ct; ct.state = lds.u.seq.stateLL; ct.dnb = lds.u.seq.dnb[0]; ct.dfs = lds.u.seq.dfs[0]; ct.tableLog = 0;
-    u32 mySz = 0, myType = 0;
+    u32 mySz = 0, myType = 0, myMax = 0;
     {
         KSeqCodes const cl = kx_seq_codes(seqs[nbSeq - 1], nbSeq - 1, longType, longPos);
         KSeqCodes const cf = kx_seq_codes(seqs[0], 0, longType, longPos);
         if (lane < 3) {
             u32 const lastCode = lane == 0 ? cl.ll : lane == 1 ? cl.of : cl.ml;
             u32 const firstCode = lane == 0 ? cf.ll : lane == 1 ? cf.of : cf.ml;
-            mySz = kx_build_seq_table(lds, lane, lds.hist + 64 * lane, nbSeq, lastCode, firstCode, myType, ct, (xflags >> KXE_STRATEGY_SHIFT) ? (xflags >> KXE_STRATEGY_SHIFT) & KXE_STRATEGY_MASK : ((xflags & KXE_STRATEGY_FAST) ? 1u : 2u), prior);
+            mySz = kx_build_seq_table<LAZY>(lds, lane, lds.hist + 64 * lane, nbSeq, lastCode, firstCode, myType, ct, (xflags >> KXE_STRATEGY_SHIFT) ? (xflags >> KXE_STRATEGY_SHIFT) & KXE_STRATEGY_MASK : ((xflags & KXE_STRATEGY_FAST) ? 1u : 2u), prior, prev, &myMax);
         }
     }
     kx_sync();
@@ -951,6 +997,10 @@ KX_DEV u32 kzstd_sequences(KEntropyLds& lds, u8* dst, const KSeq* seqs, u32 nbSe
     u32 const ty0 = kx_shfl(myType, 0), ty1 = kx_shfl(myType, 1), ty2 = kx_shfl(myType, 2);
     u32 const tl0 = kx_shfl(ct.tableLog, 0), tl1 = kx_shfl(ct.tableLog, 1), tl2 = kx_shfl(ct.tableLog, 2);
     if (sz0 == KXE_ERR || sz1 == KXE_ERR || sz2 == KXE_ERR) return 0;
+    if (LAZY && choice) {
+        choice->type[0] = ty0; choice->type[1] = ty1; choice->type[2] = ty2; choice->log[0] = tl0; choice->log[1] = tl1; choice->log[2] = tl2;
+        choice->maxSym[0] = kx_shfl(myMax, 0); choice->maxSym[1] = kx_shfl(myMax, 1); choice->maxSym[2] = kx_shfl(myMax, 2);
+    }
     u8* op = dst + hdr;
     if (lane == 0) *op = (u8)((ty0 << 6) + (ty1 << 4) + (ty2 << 2));
     op++;
@@ -1317,7 +1367,46 @@ KX_DEV u32 kx_split_block_borders(KEntropyLds& lds, const u8* p, int lane)
     return (dFM > dLM) ? (32u << 10) : (96u << 10);
 }
 
-KX_DEV void zstd_frame_block(const KFrameArgs& a, KEntropyLds& lds, u32 slice, int lane)
+// ZSTD_splitBlock_byChunks at the levels the lazy strategies take: the events are a hash of two bytes (hashLog bits: 9 for greedy and lazy,
+// 10 for lazy2) sampled every `rate` bytes (11 / 5).  tab: 2 << hashLog words of LDS (chunks so far, new chunk).
+KX_DEV u32 kx_split_block_hashed(u32* tab, const u8* p, u32 rate, u32 hashLog, int lane)
+{
+    u32 const size = 1u << hashLog, nbNew = 8191u / rate; u32* const past = tab; u32* const nw = tab + size;
+    u32 nbPast = nbNew; int penalty = 3; u32 result = KX_BLOCK_MAX;
+    for (u32 i = (u32)lane; i < size; i += 64u) past[i] = 0;
+    kx_sync();
+    for (u32 j = (u32)lane; j * rate < 8191u; j += 64u) kx_lds_inc(&past[(((u32)p[j * rate] | ((u32)p[j * rate + 1u] << 8)) * 0x9E3779B9u) >> (32u - hashLog)]);
+    kx_sync();
+    for (u32 pos = 8192u; pos <= KX_BLOCK_MAX - 8192u; pos += 8192u) {
+        for (u32 i = (u32)lane; i < size; i += 64u) nw[i] = 0;
+        kx_sync();
+        for (u32 j = (u32)lane; j * rate < 8191u; j += 64u) kx_lds_inc(&nw[(((u32)p[pos + j * rate] | ((u32)p[pos + j * rate + 1u] << 8)) * 0x9E3779B9u) >> (32u - hashLog)]);
+        kx_sync();
+        u32 dev = 0;
+        for (u32 i = (u32)lane; i < size; i += 64u) {
+            int const d = (int)(past[i] * nbNew) - (int)(nw[i] * nbPast);
+            dev += (u32)(d < 0 ? -d : d);
+        }
+        dev = kx_wave_sum(dev, lane);
+        u32 const threshold = (u32)(((u64)nbPast * nbNew * (u32)(14 + penalty)) / 16u);
+        if (dev >= threshold) { result = pos; break; }
+        for (u32 i = (u32)lane; i < size; i += 64u) past[i] += nw[i];
+        nbPast += nbNew;
+        if (penalty > 0) penalty--;
+        kx_sync();
+    }
+    kx_sync();
+    return result;
+}
+
+// What a block of a frame at levels 5 .. 10 brings to the frame step besides KFrameArgs (zstd_lazy_big.h): the slice's strategy (3 greedy,
+// 4 lazy, 5 lazy2) and window, its previous sequence tables, LDS for the pre-splitter's two fingerprints (2 048 words)
+struct KLazyFrame { u32 strat, windowLog; KSeqPrev* prev; u32* split; };
+
+// LAZY: levels 5 .. 10 (lz: never null then) -- literals gathered here and coded without preferRepeat from strategy "lazy" on, sequence
+// tables priced against the previous block's, the pre-splitter of these strategies.  The instantiation without it is what levels <= 4 run.
+template <bool LAZY = false>
+KX_DEV void zstd_frame_block(const KFrameArgs& a, KEntropyLds& lds, u32 slice, int lane, const KLazyFrame* lz = nullptr)
 {
     KFrameState fs = a.fstate[slice];
     if (fs.blockSize == 0) return;                       // frame finished in an earlier round
@@ -1330,7 +1419,7 @@ KX_DEV void zstd_frame_block(const KFrameArgs& a, KEntropyLds& lds, u32 slice, i
     // the window a frame of known size is written with: level 3's 2^21 at most, or the "fast" level's own (2^19 / 2^20), past which the
     // header carries a window descriptor instead of the single-segment flag
     u32 const fastLevel = a.fast_step0 ? 0u : a.level2 ? 2u : 1u;
-    u32 const wlogKnown = a.strategy ? kx_window_log_fast(fastLevel, n, false) : 21u;
+    u32 const wlogKnown = LAZY ? lz->windowLog : a.strategy ? kx_window_log_fast(fastLevel, n, false) : 21u;
     if (fs.ipos == 0 && streaming) {
         // streaming frame header: no content size, window descriptor for 2^21
         if (lane == 0) { kx_st32(dst, 0xFD2FB528u); dst[4] = 0; dst[5] = (u8)(((a.strategy ? (a.level2 ? 20 : 19) : 21) - 10) << 3); }
@@ -1347,19 +1436,21 @@ KX_DEV void zstd_frame_block(const KFrameArgs& a, KEntropyLds& lds, u32 slice, i
     u32 cSize = 0;
     KSliceMeta mm; mm.nbSeq = 0; mm.litSize = 0; mm.lastLL = bs; mm.longType = 0; mm.longPos = 0; mm.status = 0; mm.pad[0] = fs.rep[0]; mm.pad[1] = fs.rep[1];
     KHufPrev hp; hp.ct = hufct + 256u * fs.hufSel; hp.valid = fs.hufValid != 0; hp.newCt = hufct + 256u * (fs.hufSel ^ 1u); hp.outcome = 0;
+    KSeqChoice choice; for (int t = 0; t < 3; t++) { choice.type[t] = KSET_REPEAT; choice.maxSym[t] = 0; choice.log[t] = 0; }      // (LAZY only; no sequences: the tables stay)
     if (bs >= 7) {                                       // MIN_CBLOCK_SIZE + block header + 1 + 1
         mm = a.meta[slice];
         if (mm.status != 0 && lane == 0 && a.status_word) kx_atomic_or(a.status_word, 2u);          // (never expected; the frame cannot be trusted)
         const KSeq* const seqs = a.seqs + (size_t)slice * a.seq_cap;
         u8* const lits = a.lits + (size_t)slice * a.lit_cap;
         u32 const litSize = mm.litSize + mm.lastLL;
-        if (a.strategy) kx_gather_literals(lits, bsrc, bs, seqs, mm.nbSeq, mm.longType, mm.longPos, lane);   // the level-1 parse stores no literals
+        if (LAZY || a.strategy) kx_gather_literals(lits, bsrc, bs, seqs, mm.nbSeq, mm.longType, mm.longPos, lane);   // the level-1 parse stores no literals
         kx_wave_copy(lits + mm.litSize, bsrc + (bs - mm.lastLL), mm.lastLL, lane);
         kx_sync();
         bool const suspect = (mm.nbSeq == 0) || (litSize / mm.nbSeq >= 20);
-        u32 const litSec = kzstd_literals(lds, body, lits, litSize, suspect, a.scratch + (size_t)slice * a.scratch_words, lane, &hp, a.fast_step0 != 0);
+        u32 const litSec = kzstd_literals(lds, body, lits, litSize, suspect, a.scratch + (size_t)slice * a.scratch_words, lane, &hp, a.fast_step0 != 0, LAZY ? lz->strat < 4u : true);
         kx_sync();
-        u32 const seqSec = kzstd_sequences(lds, body + litSec, seqs, mm.nbSeq, mm.longType, mm.longPos, lane, litSec < bs ? bs - litSec : 0u, a.strategy ? 32u : 0u);
+        u32 const seqSec = LAZY ? kzstd_sequences<true>(lds, body + litSec, seqs, mm.nbSeq, mm.longType, mm.longPos, lane, litSec < bs ? bs - litSec : 0u, lz->strat << KXE_STRATEGY_SHIFT, nullptr, lz->prev, &choice)
+                                : kzstd_sequences(lds, body + litSec, seqs, mm.nbSeq, mm.longType, mm.longPos, lane, litSec < bs ? bs - litSec : 0u, a.strategy ? 32u : 0u);
         if (seqSec != 0) {
             cSize = litSec + seqSec;
             if (cSize >= bs - kx_min_gain(bs)) cSize = 0;
@@ -1388,6 +1479,15 @@ KX_DEV void zstd_frame_block(const KFrameArgs& a, KEntropyLds& lds, u32 slice, i
         // ZSTD_blockState_confirmRepcodesAndEntropyTables
         fs.rep[0] = mm.pad[0]; fs.rep[1] = mm.pad[1];
         if (hp.outcome == 2) { fs.hufSel ^= 1u; fs.hufValid = 1; }
+        if (LAZY && lane < 3) {
+            // ... and the sequence tables: a new one is the next block's candidate, the default and run-length ones leave none (lds.norm still
+            // holds what the table was built from)
+            u32 const ty = choice.type[lane];
+            if (ty == KSET_COMPRESSED) {
+                lz->prev->mode[lane] = 1; lz->prev->maxSym[lane] = choice.maxSym[lane]; lz->prev->log[lane] = choice.log[lane];
+                for (u32 s = 0; s <= choice.maxSym[lane]; s++) lz->prev->norm[lane][s] = lds.norm[lane][s];
+            } else if (ty != KSET_REPEAT) lz->prev->mode[lane] = 0;
+        }
     }
     fs.savings += (int)bs - (int)outSize;
     fs.ipos += bs; fs.opos += outSize; fs.first = 0;
@@ -1397,10 +1497,11 @@ KX_DEV void zstd_frame_block(const KFrameArgs& a, KEntropyLds& lds, u32 slice, i
     if (a.stream && fs.ipos == KX_BLOCK_MAX) fs.savings -= streaming ? 6 : (int)kx_frame_header_size(n, wlogKnown);
     if (fs.ipos < n) {
         // the window of the level: beyond it libzstd's staging buffer wraps and the window slides (the "fast" levels too, since round 4)
-        u32 const windowLog = a.strategy ? kx_window_log_fast(fastLevel, n, streaming) : (streaming ? 21u : a.level2 ? 18u : kx_params_l3(n).windowLog);
+        u32 const windowLog = LAZY ? lz->windowLog : a.strategy ? kx_window_log_fast(fastLevel, n, streaming) : (streaming ? 21u : a.level2 ? 18u : kx_params_l3(n).windowLog);
         u32 const remaining = kx_frame_window_step(fs, n, a.stream, windowLog, a.tail_direct, a.out_chunk);
         if (remaining < KX_BLOCK_MAX) next = remaining;
         else if (fs.savings < 3) next = KX_BLOCK_MAX;
+        else if (LAZY) next = lz->strat >= 5u ? kx_split_block_hashed(lz->split, src + fs.ipos, 5u, 10u, lane) : kx_split_block_hashed(lz->split, src + fs.ipos, 11u, 9u, lane);
         else next = a.strategy ? kx_split_block_borders(lds, src + fs.ipos, lane) : kx_split_block(lds, src + fs.ipos, lane);
     }
     fs.blockSize = next;

@@ -5,6 +5,7 @@
 #include "zstd_entropy.h"           // (brings zstd_match.h, zstd_match_ext.h, zstd_match_fast.h)
 #include "zstd_match_dict.h"
 #include "zstd_lazy.h"
+#include "zstd_lazy_big.h"
 #include <type_traits>
 
 // The parsers are templates on their team width (lanes per slice): f(std::integral_constant<int, G>()) for G = 2 .. 64 (else 64)
@@ -133,6 +134,17 @@ inline KFrameArgs kx_frame_args(KBatchView const& v, KFrameState* fstate, u32* h
     e.fast_step0 = b.strategy == 1u ? b.fast_step0 : 0u;
     e.tail_direct = stream == KXF_REFERENCE ? 0u : tail_or_chunk; e.out_chunk = stream == KXF_REFERENCE ? tail_or_chunk : 0u;
     return e;
+}
+// Levels 5 .. 10 over frames of several blocks (zstd_lazy_big.h): the view's slices over table slots of slot_bytes each and their
+// previous-table records; hash_log_max: kx_lazy_big_hash_log_max of the largest slice the slots must hold
+inline u64 kx_lazy_big_slot_bytes(u32 hash_log_max) { return (u64)5 << hash_log_max; }
+inline KLazyBigArgs kx_lazy_big_args(KBatchView const& v, KFrameState* fstate, u32* hufct, u32* remaining, u32* status_word, u8* tables, u64 slot_bytes, KSeqPrev* prev, int level)
+{
+    KLazyBigArgs g;
+    KBigLevel const none = { 0u, 0u, false };
+    g.e = kx_frame_args(v, fstate, hufct, remaining, status_word, KXF_ONE_SHOT, none, 0);
+    g.level = (u32)level; g.tables = tables; g.slot_bytes = slot_bytes; g.prev = prev; g.seqs_w = v.seqs; g.meta_w = v.meta;
+    return g;
 }
 // the block-chain kernels' arguments (a wave walks a slice's chain of blocks); counters: one work queue head per workgroup
 inline KBigArgs kx_big_args(KMatchArgs const& m, KFrameArgs const& e, u32* counters, u32 spw) { KBigArgs g; g.m = m; g.e = e; g.counters = counters; g.spw = spw; return g; }
