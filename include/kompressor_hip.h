@@ -51,8 +51,9 @@ KMP_API kmp_zstd_cctx* kmp_zstd_create_cctx(void);
 /* replaces ZSTD_freeCCtx              (Wrapper.cpp:19-27)  */
 KMP_API size_t kmp_zstd_free_cctx(kmp_zstd_cctx* cctx);
 /* replaces ZSTD_CCtx_setParameter     (Wrapper.cpp:29-39). Levels -131072 .. -1 and 1 .. 10 (0 = default = 3) run on the GPU where
- * kmp_zstd_compress_batch_level serves them (dictionaries: level 3 only; levels 5 .. 10: one closing call of at most 128 KiB -- 9 and 10
- * above 16 KiB --, or of up to 2 MiB when the call's output slice has room for kmp_zstd_compress_bound of it; what is not served surfaces when the stream closes); levels 11 and up return (size_t)-40 "Unsupported parameter". */
+ * kmp_zstd_compress_batch_level serves them (dictionaries: level 3 only; levels 5 .. 10: streams of up to 2 MiB, or one closing call of
+ * at most 128 KiB -- 9 and 10 above 16 KiB --, or of up to 2 MiB when the call's output slice has room for kmp_zstd_compress_bound of it; what
+ * is not served surfaces when the stream closes); levels 11 and up return (size_t)-40 "Unsupported parameter". */
 KMP_API size_t kmp_zstd_cctx_set_parameter(kmp_zstd_cctx* cctx, int param, int value);
 /* replaces ZSTD_CCtx_loadDictionary   (Wrapper.cpp:41-56). Served: dictionaries of 8 .. 130 560 bytes for slices <= 128 KiB, raw content
  * or zstd's own format (magic EC30A437: what `zstd --train` / ZDICT_trainFromBuffer write -- its Huffman and FSE tables, repeat offsets
@@ -71,8 +72,11 @@ KMP_API size_t kmp_zstd_cctx_load_dictionary(kmp_zstd_cctx* cctx, const void* di
  * and data that arrived with e_continue makes it a streaming frame (no content size).  Input is collected until e_end;
  * streams up to 1 GiB at every served level (beyond a level's window -- 512 KiB at level 1 and the negative levels, 1 MiB
  * at level 2, 2 MiB at levels 3 and 4 -- the window slides as libzstd's does).
- * Levels 5 .. 10 above 128 KiB: only the in-place case is served (e_end with nothing staged, room for kmp_zstd_compress_bound, 128 KiB + 1 ..
- * 2 MiB, no dictionary); staged chunks, data that arrived with e_continue and a loaded dictionary return "Unsupported parameter". */
+ * Levels 5 .. 10, no dictionary: data that arrived with e_continue makes a streaming frame of up to 2 MiB in all (the unknown-size
+ * parameters at every length; closed with or without data); a single closing call (e_end, nothing staged) is served up to 128 KiB and,
+ * in place, from 128 KiB + 1 to 2 MiB when its output slice has room for kmp_zstd_compress_bound.  Still refused with "Unsupported
+ * parameter": streams beyond 2 MiB, a loaded dictionary, and the one remaining step -- the single closing call of more than 128 KiB whose
+ * output slice lacks room for the bound (libzstd stages it; kmp_zstd_compress_batch_reference writes exactly those frames meanwhile). */
 KMP_API size_t kmp_zstd_compress_stream(kmp_zstd_cctx* cctx,
                                         void* dst, size_t dst_size, size_t* dst_pos,
                                         const void* src, size_t src_size, size_t* src_pos,
@@ -237,7 +241,8 @@ KMP_API int kmp_zstd_compress_batch_stream_level(kmp_batch_ctx* ctx,
  * but stages it in chunks of 128 KiB -- the block pre-splitter sees one chunk at a time, and beyond the window + 128 KiB
  * the staging buffer wraps and the window slides.  Frames differ from kmp_zstd_compress_batch's
  * wherever the pre-splitter cuts; up to 128 KiB they are the same.  Levels -131072 .. -1 and 1 .. 4 (0 = 3), any size the
- * context holds.  out_chunk: size of the caller's output slices if it is not the reference's (0 = max(8192, n / 10)). */
+ * context holds; levels 5 .. 10 up to 2 MiB (one block up to 128 KiB, staged frames above; a larger slice is refused per slice: out_len 0,
+ * KMP_STATUS_LEVEL_SIZE; 9 and 10 up to 16 KiB as in kmp_zstd_compress_batch_level).  out_chunk: size of the caller's output slices if it is not the reference's (0 = max(8192, n / 10)). */
 KMP_API int kmp_zstd_compress_batch_reference(kmp_batch_ctx* ctx,
                                               const void* d_src, const uint64_t* d_in_off, const uint32_t* d_in_len,
                                               uint32_t n,
@@ -265,8 +270,10 @@ KMP_API int kmp_zstd_compress_batch_reference(kmp_batch_ctx* ctx,
  * levels 9 and 10 a slice of 8 bytes .. 16 KiB is strategy "btlazy2": refused as above.  The first batch at these levels allocates their
  * workspace (16 bytes per position of up to 16 384 slices; on a context for larger slices also libzstd's own row tables, 5 bytes << hashLog
  * -- 2.5 MiB a slice up to 256 KiB, 20 MiB at 2 MiB -- for the slices in flight: what 8 GiB hold, 4 096 at most, KMP_LAZY_BIG_SLICES caps
- * it; a larger batch goes through in pieces).  Not served at these levels: streams, kmp_zstd_compress_batch_reference's staged frames,
- * dictionaries. */
+ * it; a larger batch goes through in pieces).  The same kernel family writes these levels' streams (kmp_zstd_compress_batch_stream_level:
+ * 0 .. 2 MiB under the unknown-size parameters, table slots of 5 bytes << the level's hashLog whatever the length -- 2.5 MiB at levels 5 and
+ * 6, 20 MiB at level 10; a part made with smaller slots is made once more) and the reference driver's staged frames
+ * (kmp_zstd_compress_batch_reference).  Not served at these levels: slices above 2 MiB, dictionaries. */
 KMP_API int kmp_zstd_compress_batch_level(kmp_batch_ctx* ctx,
                                           const void* d_src, const uint64_t* d_in_off, const uint32_t* d_in_len,
                                           uint32_t n,

@@ -176,10 +176,11 @@ class ZstdBatch:
         2 MiB (frames of several blocks, as ZSTD_compress2 writes them) -- at 9 and 10 a slice of 8 bytes .. 16 KiB is another strategy and
         comes back refused (out_len 0, status bit 4), as do a slice above 2 MiB at levels 5 .. 10 and a level-4 slice between 128 and 256 KiB.
         streaming: None = one-shot frames; "data" / "empty" = the frames of slices that arrived through finish = false
-        calls, closed by a call with / without data (context created for slices above 128 KiB; levels 1 to 3).
+        calls, closed by a call with / without data (context created for slices above 128 KiB; levels 1 to 4 and the negative ones at
+        any length, 5 .. 10 for streams of 0 .. 2 MiB -- a longer one comes back refused: out_len 0, status bit 4).
         reference: the frames ZstdCompressor(level).transform(bytes) returns -- above 128 KiB the reference's output slices
         make libzstd stage the input in 128 KiB chunks, so they differ from ZSTD_compress2's (the default here) wherever
-        the block pre-splitter cuts (no dictionary); up to 128 KiB both are the same.
+        the block pre-splitter cuts (no dictionary); up to 128 KiB both are the same.  Levels 5 .. 10: up to 2 MiB, as above.
         Returns (dst, out_off, out_len): frame i = dst[out_off[i] : out_off[i] + out_len[i]]."""
         n = in_len.numel()
         if dst is None:

@@ -50,6 +50,21 @@ __global__ __launch_bounds__(256) void k_zstd_lazy_big_init(const u32* in_len, u
     if (refused) { out_len[i] = 0; atomicOr(status, (u32)KMP_STATUS_LEVEL_SIZE); }
     else if (s.blockSize) atomicAdd(remaining, 1u);
 }
+// ... as streams or as the reference driver's staged frames (KFrameArgs.stream = KXF_STREAM / KXF_STREAM_EMPTY_END / KXF_REFERENCE): a kernel of
+// its own, so that the one-shot kernel keeps its code
+__global__ __launch_bounds__(64, 2) void k_zstd_lazy_big_modes(KLazyBigArgs a) { zstd_lazy_big_body<true>(a); }
+// ... and its init: a stream is taken at every length (an empty one: its nine bytes are written here)
+__global__ __launch_bounds__(256) void k_zstd_lazy_big_init_modes(const u32* in_len, u32 n, KFrameState* fs, KSeqPrev* prev, u8* dst, const u64* out_off, u32* out_len, u32* remaining, u32* status, u32 mode, u32 level)
+{
+    u32 const i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    KFrameState s; bool refused;
+    zstd_lazy_big_init_slice(in_len[i], s, prev[i], refused, mode);
+    fs[i] = s;
+    if (refused) { out_len[i] = 0; atomicOr(status, (u32)KMP_STATUS_LEVEL_SIZE); }
+    else if (s.blockSize) atomicAdd(remaining, 1u);
+    else if (mode != KXF_REFERENCE) out_len[i] = zstd_lazy_big_empty_stream(dst + out_off[i], level);
+}
 // ... of a batch parsed against a formatted dictionary: its tables as the block's predecessor, its ID in the frame header
 __global__ __launch_bounds__(64, 4) void k_zstd_entropy_prior(KEntropyArgs a) { zstd_entropy_body<true>(a); }
 #ifdef KMP_ABLATIONS
@@ -233,7 +248,7 @@ __global__ __launch_bounds__(64) void k_table_probe(u32* p0, u32* p1, u32* p2, u
     }
     if (acc == 0x12345678u) sink[0] = acc;
 }
-extern "C" const char* kmp_version(void) { return "kompressor_hip 0.4 (gfx950; zstd levels -131072 .. -1 and 1 .. 3: frames and streams up to 1 GiB, dictionaries (raw content and zstd format); level 4 up to 128 KiB, above 256 KiB and streams; levels 5 .. 10 up to 2 MiB (frames, not streams); deflate / zlib / gzip levels 1-9, windowBits 9-15, memLevel 1-9; zstd and inflate decoders)"; }
+extern "C" const char* kmp_version(void) { return "kompressor_hip 0.4 (gfx950; zstd levels -131072 .. -1 and 1 .. 3: frames and streams up to 1 GiB, dictionaries (raw content and zstd format); level 4 up to 128 KiB, above 256 KiB and streams; levels 5 .. 10 up to 2 MiB (one-shot and staged frames, streams); deflate / zlib / gzip levels 1-9, windowBits 9-15, memLevel 1-9; zstd and inflate decoders)"; }
 
 u32 env_u32(const char* name, u32 dflt)
 {
@@ -671,7 +686,7 @@ static int zstd_compress_dfast(kmp_batch_ctx* c, const void* d_src, const uint64
 static int lazy_workspace(kmp_batch_ctx* c, u32 need_bytes);
 static int lazy_parse(kmp_batch_ctx* c, hipStream_t st, KBatchView const& v, int level);
 static int zstd_compress_lazy_big(kmp_batch_ctx* c, const void* d_src, const uint64_t* d_in_off, const uint32_t* d_in_len,
-                                  uint32_t n, void* d_dst, const uint64_t* d_out_off, uint32_t* d_out_len, hipStream_t st, int level);
+                                  uint32_t n, void* d_dst, const uint64_t* d_out_off, uint32_t* d_out_len, hipStream_t st, int level, u32 mode = KXF_ONE_SHOT, u32 out_chunk = 0);
 static int zstd_compress_lazy(kmp_batch_ctx* c, const void* d_src, const uint64_t* d_in_off, const uint32_t* d_in_len,
                               uint32_t n, void* d_dst, const uint64_t* d_out_off, uint32_t* d_out_len, void* hip_stream, int level)
 {
@@ -730,11 +745,16 @@ static int lazy_parse(kmp_batch_ctx* c, hipStream_t st, KBatchView const& v, int
 // ... on a context for slices above 128 KiB.  The slices up to 128 KiB go through the one-block kernels above, which see every larger slice
 // as an empty one; then k_zstd_lazy_big walks the chains of the slices of 128 KiB + 1 .. 2 MiB, in pieces of as many slices as the part
 // holds table slots for.  A slice above 2 MiB is refused (libzstd's parameters are pinned up to there): out_len 0, KMP_STATUS_LEVEL_SIZE.
-static int lazy_big_workspace(kmp_batch_ctx* c)
+// mode (KFrameArgs.stream): the reference driver's staged frames (KXF_REFERENCE) go the same way with the input taken in chunks of 128 KiB;
+// of a batch of streams every slice, from 0 bytes on, goes through the chain kernel under the unknown-size parameters.
+// slot_bytes: what a table slot must hold for this batch.  One-shot and staged frames: by the context's largest slice; streams: by the level's
+// hashLog whatever their length (20 MiB at level 10).  A part made with smaller slots is made once more.
+static int lazy_big_workspace(kmp_batch_ctx* c, u64 slot_bytes)
 {
+    if (c->lzb && c->lzb->slot_bytes < slot_bytes) c->lzb.reset();
     if (c->lzb) return KMP_OK;
-    auto fill = [c](lazy_big_part& z) {
-        z.slot_bytes = kx_lazy_big_slot_bytes(kx_lazy_big_hash_log_max(c->max_slice_bytes));
+    auto fill = [c, slot_bytes](lazy_big_part& z) {
+        z.slot_bytes = slot_bytes;
         // slices in flight: what 8 GiB of tables hold, 4 096 at most (twice what the device runs at once); KMP_LAZY_BIG_SLICES caps it (the
         // tests run a handful of slices through fewer slots)
         u64 fit = ((u64)8 << 30) / z.slot_bytes; if (fit > 4096u) fit = 4096u;
@@ -751,35 +771,43 @@ static int lazy_big_workspace(kmp_batch_ctx* c)
     return build_part(c->lzb, KMP_PART_LAZY_BIG, fill);
 }
 static int zstd_compress_lazy_big(kmp_batch_ctx* c, const void* d_src, const uint64_t* d_in_off, const uint32_t* d_in_len,
-                                  uint32_t n, void* d_dst, const uint64_t* d_out_off, uint32_t* d_out_len, hipStream_t st, int level)
+                                  uint32_t n, void* d_dst, const uint64_t* d_out_off, uint32_t* d_out_len, hipStream_t st, int level, u32 mode, u32 out_chunk)
 {
+    bool const streaming = mode == KXF_STREAM || mode == KXF_STREAM_EMPTY_END;
     KMP_TRY(batch_begin(c, st, d_in_len, n, c->max_slice_bytes));
-    KMP_TRY(lazy_big_workspace(c));
-    KMP_TRY(lazy_workspace(c, KMP_MAX_SLICE_BYTES));
+    KMP_TRY(lazy_big_workspace(c, kx_lazy_big_slot_bytes_mode(c->max_slice_bytes, level, mode)));
+    if (!streaming) KMP_TRY(lazy_workspace(c, KMP_MAX_SLICE_BYTES));
     lazy_big_part const& z = *c->lzb;
     KBatchView const v = batch_view(c, d_src, d_in_off, n, d_dst, d_out_off, d_out_len);
-    // the one-block slices (the others: empty frames there, replaced below)
-    hipLaunchKernelGGL(k_zstd_lazy_small_len, dim3((n + 255) / 256), dim3(256), 0, st, v.in_len, n, z.small_len.p);
-    HIP_TRY(hipGetLastError());
-    KBatchView sv = v; sv.in_len = z.small_len;
-    KMP_TRY(lazy_parse(c, st, sv, level));
-    KEntropyArgs const e = kx_entropy_args(sv, kx_entropy_flags_lazy(level));
-    hipLaunchKernelGGL(k_zstd_entropy, dim3(n), dim3(64), 0, st, e);
-    HIP_TRY(hipGetLastError());
+    if (!streaming) {
+        // the one-block slices (the others: empty frames there, replaced below); staged = in place up to 128 KiB
+        hipLaunchKernelGGL(k_zstd_lazy_small_len, dim3((n + 255) / 256), dim3(256), 0, st, v.in_len, n, z.small_len.p);
+        HIP_TRY(hipGetLastError());
+        KBatchView sv = v; sv.in_len = z.small_len;
+        KMP_TRY(lazy_parse(c, st, sv, level));
+        KEntropyArgs const e = kx_entropy_args(sv, kx_entropy_flags_lazy(level));
+        hipLaunchKernelGGL(k_zstd_entropy, dim3(n), dim3(64), 0, st, e);
+        HIP_TRY(hipGetLastError());
+    }
     // the frames of several blocks
     HIP_TRY(hipMemsetAsync(c->remaining, 0, 4, st));
     for (u32 first = 0; first < n; first += z.chunk) {
         u32 const m = (n - first < z.chunk) ? n - first : z.chunk;
         KBatchView const pv = v.sub(first, m);
-        hipLaunchKernelGGL(k_zstd_lazy_big_init, dim3((m + 255) / 256), dim3(256), 0, st, pv.in_len, m, c->fstate + first, z.prev.p, pv.out_len, c->remaining.p, c->d_status.p);
-        KLazyBigArgs const g = kx_lazy_big_args(pv, c->fstate + first, c->hufct + (size_t)first * 512u, c->remaining, c->d_status, z.tables, z.slot_bytes, z.prev, level);
-        hipLaunchKernelGGL(k_zstd_lazy_big, dim3(m), dim3(64), 0, st, g);
+        KLazyBigArgs const g = kx_lazy_big_args(pv, c->fstate + first, c->hufct + (size_t)first * 512u, c->remaining, c->d_status, z.tables, z.slot_bytes, z.prev, level, mode, out_chunk);
+        if (mode == KXF_ONE_SHOT) {
+            hipLaunchKernelGGL(k_zstd_lazy_big_init, dim3((m + 255) / 256), dim3(256), 0, st, pv.in_len, m, c->fstate + first, z.prev.p, pv.out_len, c->remaining.p, c->d_status.p);
+            hipLaunchKernelGGL(k_zstd_lazy_big, dim3(m), dim3(64), 0, st, g);
+        } else {
+            hipLaunchKernelGGL(k_zstd_lazy_big_init_modes, dim3((m + 255) / 256), dim3(256), 0, st, pv.in_len, m, c->fstate + first, z.prev.p, pv.dst, pv.out_off, pv.out_len, c->remaining.p, c->d_status.p, mode, (u32)level);
+            hipLaunchKernelGGL(k_zstd_lazy_big_modes, dim3(m), dim3(64), 0, st, g);
+        }
         HIP_TRY(hipGetLastError());
     }
     c->last_rounds = 0; c->last_chunks = 1; c->zstd_timed = 0;
     // (the per-slice records: of the one-block slices what their parser left -- "not served" at levels 9 and 10 up to 16 KiB --, of the others
-    // their last block's)
-    return batch_end(c, st, d_in_len, n, c->max_slice_bytes, d_out_len, c->meta);
+    // their last block's; a batch of streams has none for its shortest slices, and a tripped guard is in the status word already)
+    return batch_end(c, st, d_in_len, n, c->max_slice_bytes, d_out_len, streaming ? nullptr : c->meta);
 }
 
 extern "C" int kmp_zstd_compress_batch_level(kmp_batch_ctx* c, const void* d_src, const uint64_t* d_in_off, const uint32_t* d_in_len,
@@ -999,12 +1027,14 @@ extern "C" int kmp_zstd_compress_batch_stream_level(kmp_batch_ctx* c, const void
 {
     if (level == 0) level = 3;
     bool const neg = level < 0;
-    if ((level < 1 && !neg) || level > 4 || level < -131072) { g_last_error = "kmp_zstd_compress_batch_stream_level: levels -131072 .. -1 and 1 .. 4 are served"; return KMP_ERR_ARG; }
+    if ((level < 1 && !neg) || level > 10 || level < -131072) { g_last_error = "kmp_zstd_compress_batch_stream_level: levels -131072 .. -1 and 1 .. 10 are served"; return KMP_ERR_ARG; }
     KMP_TRY(args_present("kmp_zstd_compress_batch_stream", c != nullptr, n, { d_src, d_in_off, d_in_len, d_dst, d_out_off, d_out_len }));
     if (!c->big) { g_last_error = "kmp_zstd_compress_batch_stream: the context must be created with max_slice_bytes above 128 KiB"; return KMP_ERR_CAPACITY; }
     KMP_TRY(args_count("kmp_zstd_compress_batch_stream", c, n));
     if (n == 0) return KMP_OK;
     HIP_TRY(hipSetDevice(c->device));
+    // levels 5 .. 10: streams of 0 .. 2 MiB, every one through the chain kernel of zstd_lazy_big.h (longer ones are refused per slice)
+    if (level >= 5) return zstd_compress_lazy_big(c, d_src, d_in_off, d_in_len, n, d_dst, d_out_off, d_out_len, (hipStream_t)hip_stream, level, empty_end ? KXF_STREAM_EMPTY_END : KXF_STREAM, 0);
     KBigLevel const b = kx_big_level(level);
     return zstd_compress_big(c, d_src, d_in_off, d_in_len, n, d_dst, d_out_off, d_out_len, (hipStream_t)hip_stream, empty_end ? KXF_STREAM_EMPTY_END : KXF_STREAM, b.strategy, 0, b.fast_step0, b.level4);
 }
@@ -1017,10 +1047,12 @@ extern "C" int kmp_zstd_compress_batch_reference(kmp_batch_ctx* c, const void* d
     KMP_TRY(args_present("kmp_zstd_compress_batch_reference", c != nullptr, 0, {}));
     if (!c->big) return kmp_zstd_compress_batch_level(c, d_src, d_in_off, d_in_len, n, d_dst, d_out_off, d_out_len, level, hip_stream);   // one block: one chunk
     bool const neg = level < 0;
-    if ((level < 1 && !neg) || level > 4 || level < -131072) { g_last_error = "kmp_zstd_compress_batch_reference: levels -131072 .. -1 and 1 .. 4 are served"; return KMP_ERR_ARG; }
+    if ((level < 1 && !neg) || level > 10 || level < -131072) { g_last_error = "kmp_zstd_compress_batch_reference: levels -131072 .. -1 and 1 .. 10 are served"; return KMP_ERR_ARG; }
     KMP_TRY(batch_args("kmp_zstd_compress_batch_reference", c, n, { d_src, d_in_off, d_in_len, d_dst, d_out_off, d_out_len }));
     if (n == 0) return KMP_OK;
     HIP_TRY(hipSetDevice(c->device));
+    // levels 5 .. 10: one block up to 128 KiB (staged = in place there), staged frames up to 2 MiB, larger slices refused per slice
+    if (level >= 5) return zstd_compress_lazy_big(c, d_src, d_in_off, d_in_len, n, d_dst, d_out_off, d_out_len, (hipStream_t)hip_stream, level, KXF_REFERENCE, out_chunk);
     KBigLevel const b = kx_big_level(level);
     return zstd_compress_big(c, d_src, d_in_off, d_in_len, n, d_dst, d_out_off, d_out_len, (hipStream_t)hip_stream, KXF_REFERENCE, b.strategy, out_chunk, b.fast_step0, b.level4);
 }

@@ -139,18 +139,24 @@ static size_t run_single_compress(kmp_zstd_cctx* c, size_t first_room, size_t en
     bool const in_place = first_room >= kmp_zstd_compress_bound(end_avail);
     u32 tail_direct = 0;
     if (streaming && in_place && end_avail != 0) {
-        // libzstd's staging buffer: the window of a stream of unknown size + one block (level 3 / 4: 2 MiB, level 2: 1 MiB, level 1 and
-        // the negative levels: 512 KiB)
-        size_t const lap = ((c->level == 3 || c->level == 4) ? 17u : c->level == 2 ? 9u : 5u) * (size_t)KX_BLOCK_MAX;
+        // libzstd's staging buffer: the window of a stream of unknown size + one block (levels 3 .. 8: 2 MiB, 9 and 10: 4 MiB, level 2: 1 MiB,
+        // level 1 and the negative levels: 512 KiB)
+        size_t const lap = (c->level >= 9 ? 33u : c->level >= 3 ? 17u : c->level == 2 ? 9u : 5u) * (size_t)KX_BLOCK_MAX;
         if ((n - end_avail) % lap == 0) tail_direct = (u32)end_avail;
     }
     if (streaming && !c->dict.empty()) return KERRC(ZE_parameter_unsupported);
     // level 4: what arrives in one closing call, up to 128 KiB (its greedy and double-fast rows) or above 256 KiB; the rest: CPU library
     if (c->level == 4 && (!c->dict.empty() || (!streaming && !(n <= 131072u || n > 262144u)))) return KERRC(ZE_parameter_unsupported);
-    // levels 5 .. 10 (greedy / lazy / lazy2): one closing call of at most 128 KiB, or of up to 2 MiB that libzstd compresses in place (the
-    // frames of several blocks of zstd_lazy_big.h are ZSTD_compress2's; staged input cuts its blocks elsewhere); 9 and 10 up to 16 KiB are
-    // "btlazy2": CPU library
-    if (c->level >= 5 && (!c->dict.empty() || streaming || (n > KMP_MAX_SLICE_BYTES && (!in_place || n > KX_LAZY_BIG_MAX)) || (c->level >= 9 && n <= 16384u))) return KERRC(ZE_parameter_unsupported);
+    // levels 5 .. 10 (greedy / lazy / lazy2), no dictionary.  Data that arrived with e_continue: a streaming frame of up to 2 MiB, every
+    // length through the chain kernel of zstd_lazy_big.h under the unknown-size parameters (lazy2 at 9 and 10 whatever the length).  One
+    // closing call: at most 128 KiB (9 and 10 up to 16 KiB are "btlazy2": CPU library), or up to 2 MiB that libzstd compresses in place
+    // (ZSTD_compress2's frame).  The one case left: a single closing call above 128 KiB without room for the bound, which libzstd stages --
+    // kmp_zstd_compress_batch_reference writes those frames, this entry point still refuses them
+    if (c->level >= 5) {
+        bool const served = c->dict.empty() && (streaming ? n <= KX_LAZY_BIG_MAX
+                                                : n <= KMP_MAX_SLICE_BYTES ? !(c->level >= 9 && n <= 16384u) : (in_place && n <= KX_LAZY_BIG_MAX));
+        if (!served) return KERRC(ZE_parameter_unsupported);
+    }
     if (c->level < 0 && !c->dict.empty()) return KERRC(ZE_parameter_unsupported);
     // the plain case -- level 3, no dictionary, the whole slice at once, one block -- joins whatever other contexts are
     // closing right now: one batch for all of them (kmp_coalesce.h); the frame is the one this context would get alone

@@ -1405,7 +1405,8 @@ struct KLazyFrame { u32 strat, windowLog; KSeqPrev* prev; u32* split; };
 
 // LAZY: levels 5 .. 10 (lz: never null then) -- literals gathered here and coded without preferRepeat from strategy "lazy" on, sequence
 // tables priced against the previous block's, the pre-splitter of these strategies.  The instantiation without it is what levels <= 4 run.
-template <bool LAZY = false>
+// LAZY_MODES: ... in any KFrameArgs.stream mode (a streaming frame's header names the window of the level's row); without it KXF_ONE_SHOT only
+template <bool LAZY = false, bool LAZY_MODES = false>
 KX_DEV void zstd_frame_block(const KFrameArgs& a, KEntropyLds& lds, u32 slice, int lane, const KLazyFrame* lz = nullptr)
 {
     KFrameState fs = a.fstate[slice];
@@ -1421,8 +1422,8 @@ KX_DEV void zstd_frame_block(const KFrameArgs& a, KEntropyLds& lds, u32 slice, i
     u32 const fastLevel = a.fast_step0 ? 0u : a.level2 ? 2u : 1u;
     u32 const wlogKnown = LAZY ? lz->windowLog : a.strategy ? kx_window_log_fast(fastLevel, n, false) : 21u;
     if (fs.ipos == 0 && streaming) {
-        // streaming frame header: no content size, window descriptor for 2^21
-        if (lane == 0) { kx_st32(dst, 0xFD2FB528u); dst[4] = 0; dst[5] = (u8)(((a.strategy ? (a.level2 ? 20 : 19) : 21) - 10) << 3); }
+        // streaming frame header: no content size, window descriptor for 2^21 (the fast levels: 2^19 / 2^20; levels 5 .. 10: their row's)
+        if (lane == 0) { kx_st32(dst, 0xFD2FB528u); dst[4] = 0; dst[5] = (u8)(((LAZY_MODES ? lz->windowLog : a.strategy ? (a.level2 ? 20u : 19u) : 21u) - 10u) << 3); }
         fs.opos = 6;
     } else if (fs.ipos == 0) {
         // frame header: content size; single segment while the window covers the slice

@@ -138,13 +138,21 @@ inline KFrameArgs kx_frame_args(KBatchView const& v, KFrameState* fstate, u32* h
 // Levels 5 .. 10 over frames of several blocks (zstd_lazy_big.h): the view's slices over table slots of slot_bytes each and their
 // previous-table records; hash_log_max: kx_lazy_big_hash_log_max of the largest slice the slots must hold
 inline u64 kx_lazy_big_slot_bytes(u32 hash_log_max) { return (u64)5 << hash_log_max; }
-inline KLazyBigArgs kx_lazy_big_args(KBatchView const& v, KFrameState* fstate, u32* hufct, u32* remaining, u32* status_word, u8* tables, u64 slot_bytes, KSeqPrev* prev, int level)
+// stream: KFrameArgs.stream (KXF_ONE_SHOT: the one-shot batch call; the other modes go through zstd_lazy_big_body<true>); out_chunk: KXF_REFERENCE's
+inline KLazyBigArgs kx_lazy_big_args(KBatchView const& v, KFrameState* fstate, u32* hufct, u32* remaining, u32* status_word, u8* tables, u64 slot_bytes, KSeqPrev* prev, int level,
+                                     u32 stream = KXF_ONE_SHOT, u32 out_chunk = 0)
 {
     KLazyBigArgs g;
     KBigLevel const none = { 0u, 0u, false };
-    g.e = kx_frame_args(v, fstate, hufct, remaining, status_word, KXF_ONE_SHOT, none, 0);
+    g.e = kx_frame_args(v, fstate, hufct, remaining, status_word, stream, none, stream == KXF_REFERENCE ? out_chunk : 0u);
     g.level = (u32)level; g.tables = tables; g.slot_bytes = slot_bytes; g.prev = prev; g.seqs_w = v.seqs; g.meta_w = v.meta;
     return g;
+}
+// the table slot a batch in that mode needs on a context for slices of up to slice_cap bytes
+inline u64 kx_lazy_big_slot_bytes_mode(u32 slice_cap, int level, u32 stream)
+{
+    bool const streaming = stream == KXF_STREAM || stream == KXF_STREAM_EMPTY_END;
+    return kx_lazy_big_slot_bytes(streaming ? kx_lazy_big_hash_log_stream(level) : kx_lazy_big_hash_log_max(slice_cap));
 }
 // the block-chain kernels' arguments (a wave walks a slice's chain of blocks); counters: one work queue head per workgroup
 inline KBigArgs kx_big_args(KMatchArgs const& m, KFrameArgs const& e, u32* counters, u32 spw) { KBigArgs g; g.m = m; g.e = e; g.counters = counters; g.spw = spw; return g; }

@@ -39,6 +39,24 @@ KX_DEV KLazyBigPar kx_lazy_big_params(u32 level, u32 n)
     p.rowLog = p.S < 4u ? 4u : p.S > 6u ? 6u : p.S;
     return p;
 }
+// A stream (size unknown when the frame starts) gets the unknown-size row whatever its length turns out to be, 0 .. 2 MiB: the row above
+// 256 KiB without the clamps to the source size, minMatch 5 (tests/golden/zstd_lazy_stream_golden.json "params")
+KX_DEV KLazyBigPar kx_lazy_big_params_stream(u32 level, u32 n)
+{
+    KLazyBigPar p; p.W = 0; p.H = 0; p.S = 0; p.mml = 0; p.strat = 0; p.rowLog = 0;
+    if (n > KX_LAZY_BIG_MAX || level < 5u || level > 10u) return p;
+    u32 const l = level - 5u;
+    static const u32 Wt[6] = { 21, 21, 21, 21, 22, 22 };
+    static const u32 Ht[6] = { 19, 19, 20, 20, 21, 22 }; static const u32 St[6] = { 3, 3, 4, 4, 4, 5 }; static const u32 Tt[6] = { 3, 4, 4, 5, 5, 5 };
+    p.W = Wt[l]; p.H = Ht[l]; p.S = St[l]; p.mml = 5; p.strat = Tt[l];
+    p.rowLog = p.S < 4u ? 4u : p.S > 6u ? 6u : p.S;
+    return p;
+}
+// mode: KFrameArgs.stream.  The staged frames of the reference's driver (KXF_REFERENCE) know their size: the parameters of the one-shot frames
+KX_DEV KLazyBigPar kx_lazy_big_params_mode(u32 level, u32 n, u32 mode)
+{
+    return (mode == KXF_STREAM || mode == KXF_STREAM_EMPTY_END) ? kx_lazy_big_params_stream(level, n) : kx_lazy_big_params(level, n);
+}
 // the largest hashLog a slice of up to cap bytes can get (level 10): what a slice's table slot is sized by (5 bytes << this)
 inline u32 kx_lazy_big_hash_log_max(u32 cap)
 {
@@ -47,6 +65,8 @@ inline u32 kx_lazy_big_hash_log_max(u32 cap)
     u32 srcLog = 0; while ((1u << srcLog) < cap) srcLog++;
     return srcLog + 1u < 22u ? srcLog + 1u : 22u;
 }
+// ... and a stream's at a level, whatever its length
+inline u32 kx_lazy_big_hash_log_stream(int level) { static const u32 Ht[6] = { 19, 19, 20, 20, 21, 22 }; return (level >= 5 && level <= 10) ? Ht[level - 5] : 22u; }
 
 struct KLazyBigArgs {
     KFrameArgs e;                 // the frame step's arguments (strategy / level2 / cls unused)
@@ -264,6 +284,9 @@ KX_DEV void kzlb_parse_block(const u8* src, u32 b0, u32 bs, u32* hashTable, u8* 
 // One wave per slice: clear the slice's tables, then parse and frame step alternate until the frame is closed.  Slices this path does not
 // take (k_zstd_lazy_big_init left their blockSize 0: 128 KiB or less -- the one-block kernels have written their frames --, above 2 MiB:
 // refused) are passed over.
+// MODES: a.e.stream may be any KXF_* mode -- streams (every length from 1 byte on: the unknown-size parameters) and the reference driver's
+// staged frames (input taken in chunks of 128 KiB: kx_frame_window_step).  Without it: KXF_ONE_SHOT, the kernel of the one-shot batch call.
+template <bool MODES = false>
 KX_DEV void zstd_lazy_big_body(const KLazyBigArgs& a)
 {
     KX_SHARED KEntropyLds lds;
@@ -273,7 +296,7 @@ KX_DEV void zstd_lazy_big_body(const KLazyBigArgs& a)
         u32 const slice = kx_xcd_chunk(it, a.e.n_slices);
         if (a.e.fstate[slice].blockSize == 0) continue;                      // (uniform)
         u32 const n = a.e.in_len[slice];
-        KLazyBigPar const P = kx_lazy_big_params(a.level, n);
+        KLazyBigPar const P = MODES ? kx_lazy_big_params_mode(a.level, n, a.e.stream) : kx_lazy_big_params(a.level, n);
         if (P.strat == 0) continue;                                          // (cannot happen: the init kernel applies the same rule)
         const u8* const src = a.e.src + a.e.in_off[slice];
         u8* const slot = a.tables + (u64)slice * a.slot_bytes;
@@ -292,19 +315,30 @@ KX_DEV void zstd_lazy_big_body(const KLazyBigArgs& a)
             if (fs.blockSize == 0) break;
             if (fs.blockSize >= 7u) kzlb_parse_block(src, fs.ipos, fs.blockSize, hashTable, tagTable, P, l2, st, fs.rep[0], fs.rep[1], seqs, a.e.seq_cap, a.meta_w + slice, lane);
             kx_sync();
-            zstd_frame_block<true>(a.e, lds, slice, lane, &lz);
+            zstd_frame_block<true, MODES>(a.e, lds, slice, lane, &lz);
             kx_sync();
         }
     }
 }
 
 // k_zstd_frame_init's sibling for a batch at levels 5 .. 10 on a context for slices above 128 KiB: the frame state of the slices this
-// path takes; blockSize 0 for the others; a slice above 2 MiB is refused (out_len 0, the status bit)
-KX_DEV void zstd_lazy_big_init_slice(u32 len, KFrameState& s, KSeqPrev& pv, bool& refused)
+// path takes; blockSize 0 for the others; a slice above 2 MiB is refused (out_len 0, the status bit).
+// mode: KFrameArgs.stream.  Streams and staged frames take their input in chunks of 128 KiB (chunkEnd, as k_zstd_frame_init sets it for
+// levels <= 4); a stream is taken at every length -- an empty one is its header and an empty last block, which the caller writes.
+KX_DEV void zstd_lazy_big_init_slice(u32 len, KFrameState& s, KSeqPrev& pv, bool& refused, u32 mode = KXF_ONE_SHOT)
 {
     s.ipos = 0; s.opos = 0; s.blockSize = 0; s.first = 1; s.rep[0] = 1; s.rep[1] = 4; s.rep[2] = 8; s.hufValid = 0; s.hufSel = 0; s.savings = 0;
-    s.lowLimit = 2; s.dictLimit = 2; s.bufPos = 0; s.extBase = 0; s.wflags = 0; s.chunkEnd = len;
+    s.lowLimit = 2; s.dictLimit = 2; s.bufPos = 0; s.extBase = 0; s.wflags = 0;
+    s.chunkEnd = (mode != KXF_ONE_SHOT && len > KX_BLOCK_MAX) ? KX_BLOCK_MAX : len;
     pv.mode[0] = 0; pv.mode[1] = 0; pv.mode[2] = 0;
     refused = len > KX_LAZY_BIG_MAX;
+    bool const streaming = mode == KXF_STREAM || mode == KXF_STREAM_EMPTY_END;
     if (len > KX_BLOCK_MAX && !refused) s.blockSize = KX_BLOCK_MAX;
+    else if (streaming && !refused) s.blockSize = len;
+}
+// the empty stream at levels 5 .. 10: no content size, the level's window descriptor, an empty last block (9 bytes)
+KX_DEV u32 zstd_lazy_big_empty_stream(u8* d, u32 level)
+{
+    kx_st32(d, 0xFD2FB528u); d[4] = 0; d[5] = (u8)((kx_lazy_big_params_stream(level, 0).W - 10u) << 3); d[6] = 1; d[7] = 0; d[8] = 0;
+    return 9u;
 }
