@@ -293,6 +293,20 @@ KMP_API int kmp_zstd_compress_batch_dict(kmp_batch_ctx* ctx,
                                          void* d_dst, const uint64_t* d_out_off, uint32_t* d_out_len,
                                          const void* h_dict, uint32_t dict_size,
                                          void* hip_stream);
+/* same at a level (what ZstdCompressor(level, dictionary) does: ZSTD_CCtx_setParameter, Wrapper.cpp:29-39, then the above).  Level 0 or 3:
+ * kmp_zstd_compress_batch_dict, bit for bit.  Levels 1, 2 and -131072 .. -1 (strategy "fast"): libzstd 1.5.7's frames again -- its CDict at
+ * these levels is one table, sized by the level's row for the dictionary alone (negative levels: row 0); slices up to 8 KiB are parsed
+ * against the attached CDict (ZSTD_compressBlock_fast_dictMatchState_generic), larger ones against its copied table
+ * (ZSTD_compressBlock_fast_extDict_generic); a negative level searches every -level-th position and leaves literals uncompressed.  The
+ * same envelope: h_dict is HOST memory, 8 .. 130 560 bytes, raw content or zstd's own format (as above, KMP_ERR_ARG for a damaged header);
+ * slices <= 128 KiB.  A context keeps the CDicts of the last four (dictionary, level class) pairs it was called with -- the classes: 3,
+ * 1, 2, negative --, so batches that alternate between them build nothing anew.  Levels 4 and up with a dictionary: KMP_ERR_ARG. */
+KMP_API int kmp_zstd_compress_batch_dict_level(kmp_batch_ctx* ctx,
+                                               const void* d_src, const uint64_t* d_in_off, const uint32_t* d_in_len,
+                                               uint32_t n,
+                                               void* d_dst, const uint64_t* d_out_off, uint32_t* d_out_len,
+                                               const void* h_dict, uint32_t dict_size,
+                                               int level, void* hip_stream);
 
 /* Inverse: n zstd frames -> n slices.  Frame i is d_src[d_in_off[i] .. +d_in_len[i]);
  * its content goes to d_dst + d_out_off[i] (capacity d_out_cap[i]); d_out_len[i]

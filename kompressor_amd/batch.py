@@ -170,8 +170,9 @@ class ZstdBatch:
     def compress(self, src, in_off, in_len, dst=None, out_off=None, out_len=None, dictionary=None, level=3, streaming=None, reference=False, check=False):
         """src: uint8 device tensor; in_off int64, in_len int32 device tensors (n each).  dictionary: bytes of a
         dictionary shared by all slices (host memory; raw content, or zstd's own format -- magic EC30A437 -- with its tables,
-        repeat offsets and ID; level 3, slices up to 128 KiB; its tables are built once per dictionary).
-        level: 3 (default); 1 / 2 / a negative level at any size the context holds (without a dictionary); 4 up to 128 KiB and above
+        repeat offsets and ID; levels 1, 2, 3 and the negative ones, slices up to 128 KiB; its tables are built once per dictionary and
+        level class -- 3, 1, 2, negative -- and the context keeps the last four).
+        level: 3 (default); 1 / 2 / a negative level at any size the context holds (with a dictionary: up to 128 KiB); 4 up to 128 KiB and above
         256 KiB; 5 .. 10 (libzstd's greedy / lazy / lazy2 parsers) for slices up to 128 KiB and, on a context created for larger slices, up to
         2 MiB (frames of several blocks, as ZSTD_compress2 writes them) -- at 9 and 10 a slice of 8 bytes .. 16 KiB is another strategy and
         comes back refused (out_len 0, status bit 4), as do a slice above 2 MiB at levels 5 .. 10 and a level-4 slice between 128 and 256 KiB.
@@ -197,14 +198,14 @@ class ZstdBatch:
         elif streaming is not None:
             rc = self.lib.kmp_zstd_compress_batch_stream_level(self._h, _ptr(src), _ptr(in_off), _ptr(in_len), n,
                                                                _ptr(dst), _ptr(out_off), _ptr(out_len), 1 if streaming == "empty" else 0, level, self._stream())
+        elif dictionary is not None:
+            if level > 3:
+                raise ValueError("levels 4 .. 10 are served without a dictionary")
+            rc = self.lib.kmp_zstd_compress_batch_dict_level(self._h, _ptr(src), _ptr(in_off), _ptr(in_len), n,
+                                                             _ptr(dst), _ptr(out_off), _ptr(out_len), bytes(dictionary), len(dictionary), level, self._stream())
         elif level not in (0, 3):
-            if dictionary is not None:
-                raise ValueError("levels 1 and 2 are served without a dictionary")
             rc = self.lib.kmp_zstd_compress_batch_level(self._h, _ptr(src), _ptr(in_off), _ptr(in_len), n,
                                                         _ptr(dst), _ptr(out_off), _ptr(out_len), level, self._stream())
-        elif dictionary is not None:
-            rc = self.lib.kmp_zstd_compress_batch_dict(self._h, _ptr(src), _ptr(in_off), _ptr(in_len), n,
-                                                       _ptr(dst), _ptr(out_off), _ptr(out_len), bytes(dictionary), len(dictionary), self._stream())
         else:
             rc = self.lib.kmp_zstd_compress_batch(self._h, _ptr(src), _ptr(in_off), _ptr(in_len), n,
                                                   _ptr(dst), _ptr(out_off), _ptr(out_len), self._stream())

@@ -78,6 +78,9 @@ __global__ __launch_bounds__(64) void k_zstd_match_fast(KFastArgs a) { zstd_matc
 // the parse when the context holds a raw-content dictionary
 template <int G>
 __global__ __launch_bounds__(64) void k_zstd_match_dict(KDictArgs a) { zstd_match_dict_body<G>(a); }
+// ... at levels 1, 2 and the negative ones (strategy "fast")
+template <int G>
+__global__ __launch_bounds__(64) void k_zstd_match_fast_dict(KFastDictArgs a) { zstd_match_fast_dict_body<G>(a); }
 #ifdef KMP_ABLATIONS
 // frames of several blocks (slices above 128 KiB): one block of every unfinished slice per launch
 template <int G>
@@ -248,7 +251,7 @@ __global__ __launch_bounds__(64) void k_table_probe(u32* p0, u32* p1, u32* p2, u
     }
     if (acc == 0x12345678u) sink[0] = acc;
 }
-extern "C" const char* kmp_version(void) { return "kompressor_hip 0.4 (gfx950; zstd levels -131072 .. -1 and 1 .. 3: frames and streams up to 1 GiB, dictionaries (raw content and zstd format); level 4 up to 128 KiB, above 256 KiB and streams; levels 5 .. 10 up to 2 MiB (one-shot and staged frames, streams); deflate / zlib / gzip levels 1-9, windowBits 9-15, memLevel 1-9; zstd and inflate decoders)"; }
+extern "C" const char* kmp_version(void) { return "kompressor_hip 0.4 (gfx950; zstd levels -131072 .. -1 and 1 .. 3: frames and streams up to 1 GiB, dictionaries (raw content and zstd format) at all of these levels up to 128 KiB; level 4 up to 128 KiB, above 256 KiB and streams; levels 5 .. 10 up to 2 MiB (one-shot and staged frames, streams); deflate / zlib / gzip levels 1-9, windowBits 9-15, memLevel 1-9; zstd and inflate decoders)"; }
 
 u32 env_u32(const char* name, u32 dflt)
 {
@@ -541,6 +544,7 @@ extern "C" void kmp_batch_destroy(kmp_batch_ctx* c)
 
 /* What the context holds on the device right now, by part (bytes): the arena (or the separate workspace allocations), the other
  * table sets, the decoders' staging, the DEFLATE workspace, the block-chain state.  Sets allocated on first use count once they exist. */
+static size_t dict_bytes(const kmp_batch_ctx* c) { size_t b = 0; for (auto const& d : c->dict) b += part_bytes(d); return b; }
 extern "C" int kmp_batch_memory(kmp_batch_ctx* c, kmp_batch_memory_info* info)
 {
     if (!c || !info || info->struct_bytes < sizeof(kmp_batch_memory_info)) { g_last_error = "kmp_batch_memory: bad argument"; return KMP_ERR_ARG; }
@@ -550,7 +554,7 @@ extern "C" int kmp_batch_memory(kmp_batch_ctx* c, kmp_batch_memory_info* info)
     if (c->arena) m.arena_used = (size_t)c->nteams * KX_TBL_ENTRIES * sizeof(u32) + ns * c->seq_cap * sizeof(KSeq) + ns * c->lit_cap + ns * sizeof(KSliceMeta) + ns * c->scratch_words * sizeof(u32);
     m.workspace = c->seqs_buf.bytes + c->lits_buf.bytes + c->meta_buf.bytes + c->scratch_buf.bytes + c->tables_buf.bytes
                 + c->team_epoch.bytes + c->counter.bytes + c->len_ok.bytes + c->d_status.bytes;
-    m.other_tables = part_bytes(c->flat) + part_bytes(c->t4) + part_bytes(c->chain_t4) + part_bytes(c->dict) + part_bytes(c->ddict) + part_bytes(c->lz) + part_bytes(c->lzb);
+    m.other_tables = part_bytes(c->flat) + part_bytes(c->t4) + part_bytes(c->chain_t4) + dict_bytes(c) + part_bytes(c->ddict) + part_bytes(c->lz) + part_bytes(c->lzb);
     m.block_chain = c->fstate.bytes + c->hufct.bytes + c->big_tables.bytes + c->remaining.bytes + c->big_counters.bytes;
     m.decode_staging = part_bytes(c->pre_seq) + part_bytes(c->pre_lit);
     m.deflate_workspace = part_bytes(c->dfl) + part_bytes(c->dflf);
@@ -870,63 +874,101 @@ int dict_header_state(const unsigned char* dict, size_t dict_size, int for_decod
     return cdict_parse_formatted(dict, dict_size, &pr, &off, for_decoder ? &dp : nullptr);
 }
 
-extern "C" int kmp_zstd_compress_batch_dict(kmp_batch_ctx* c, const void* d_src, const uint64_t* d_in_off, const uint32_t* d_in_len,
-                                            uint32_t n, void* d_dst, const uint64_t* d_out_off, uint32_t* d_out_len,
-                                            const void* h_dict, uint32_t dict_size, void* hip_stream)
+// level: 3, 1, 2 or a negative one; fn: the entry point's name for the messages
+static int zstd_compress_dict(const char* fn, kmp_batch_ctx* c, const void* d_src, const uint64_t* d_in_off, const uint32_t* d_in_len,
+                              uint32_t n, void* d_dst, const uint64_t* d_out_off, uint32_t* d_out_len,
+                              const void* h_dict, uint32_t dict_size, int level, void* hip_stream)
 {
-    KMP_TRY(batch_args("kmp_zstd_compress_batch_dict", c, n, { d_src, d_in_off, d_in_len, d_dst, d_out_off, d_out_len }, h_dict != nullptr));
-    if (c->big) { g_last_error = "kmp_zstd_compress_batch_dict: slices above 128 KiB are not served with a dictionary"; return KMP_ERR_CAPACITY; }
-    if (dict_size < 8 || dict_size > KX_MAX_DICT) { g_last_error = "kmp_zstd_compress_batch_dict: dictionary of 8 .. 130560 bytes expected"; return KMP_ERR_CAPACITY; }
+    std::string const name(fn);
+    KMP_TRY(batch_args(fn, c, n, { d_src, d_in_off, d_in_len, d_dst, d_out_off, d_out_len }, h_dict != nullptr));
+    if (c->big) { g_last_error = name + ": slices above 128 KiB are not served with a dictionary"; return KMP_ERR_CAPACITY; }
+    if (dict_size < 8 || dict_size > KX_MAX_DICT) { g_last_error = name + ": dictionary of 8 .. 130560 bytes expected"; return KMP_ERR_CAPACITY; }
     if (n == 0) return KMP_OK;
     hipStream_t const st = (hipStream_t)hip_stream;
     HIP_TRY(hipSetDevice(c->device));
-    // (re)build the CDict when the dictionary changed
+    // the CDict of this dictionary at this level class: one the context holds, else built now
+    int const cls = kx_dict_level_class(level);
     u64 hsh = 1469598103934665603ull; for (u32 i = 0; i < dict_size; i++) { hsh ^= ((const u8*)h_dict)[i]; hsh *= 1099511628211ull; }
-    if (!c->dict || c->dict->size != dict_size || c->dict->hash != hsh) {
+    int slot = -1;
+    for (int i = 0; i < KMP_DICT_SLOTS; i++) if (c->dict[i] && c->dict[i]->size == dict_size && c->dict[i]->hash == hsh && c->dict[i]->level_class == cls) slot = i;
+    if (slot < 0) {
         // A dictionary in zstd's own format (magic EC30A437) is loaded as libzstd loads it: entropy tables and repeat offsets for the first
         // block (KDictPrior), the bytes behind them as the content matches are searched in; anything else is content from its first byte.
         KDictPrior prior; size_t content_off = 0;
         int const formatted = cdict_parse_formatted((const u8*)h_dict, dict_size, &prior, &content_off);
-        if (formatted < 0) { g_last_error = "kmp_zstd_compress_batch_dict: the dictionary starts with zstd's dictionary magic but its header is damaged (libzstd: Dictionary is corrupted)"; return KMP_ERR_ARG; }
+        if (formatted < 0) { g_last_error = name + ": the dictionary starts with zstd's dictionary magic but its header is damaged (libzstd: Dictionary is corrupted)"; return KMP_ERR_ARG; }
         const u8* const content = (const u8*)h_dict + content_off; u32 const content_size = dict_size - (u32)content_off;
         HIP_TRY(hipStreamSynchronize(st));
-        c->dict.reset();
+        // into a free slot, else over the one unused longest
+        slot = 0;
+        for (int i = 0; i < KMP_DICT_SLOTS; i++) if (!c->dict[i]) { slot = i; break; } else if (c->dict[i]->used < c->dict[slot]->used) slot = i;
+        c->dict[slot].reset();
         auto fill = [&](dict_part& d) {
-            cdict_params(dict_size, &d.W, &d.C, &d.H, &d.M);        // (libzstd sizes the CDict and the frame's window by the whole dictionary, header included)
+            cdict_params(dict_size, &d.W, &d.C, &d.H, &d.M, cls);   // (libzstd sizes the CDict and the frame's window by the whole dictionary, header included)
             std::vector<u32> tl, ts;
-            cdict_fill(tl, d.H, ts, d.C, d.M, content, content_size);
+            if (cls == 3) cdict_fill(tl, d.H, ts, d.C, d.M, content, content_size);
+            else cdict_fill_fast(tl, d.H, d.C, d.M, content, content_size);
             KMP_TRY(d.content.alloc(content_size + 64, "hipMalloc(dictionary)"));
-            KMP_TRY(d.L.alloc(tl.size() * 4, "hipMalloc(dictionary tables)")); KMP_TRY(d.S.alloc(ts.size() * 4, "hipMalloc(dictionary tables)"));
+            KMP_TRY(d.L.alloc(tl.size() * 4, "hipMalloc(dictionary tables)"));
             HIP_TRY(hipMemcpy(d.content, content, content_size, hipMemcpyHostToDevice));
             HIP_TRY(hipMemcpy(d.L, tl.data(), tl.size() * 4, hipMemcpyHostToDevice));
-            HIP_TRY(hipMemcpy(d.S, ts.data(), ts.size() * 4, hipMemcpyHostToDevice));
+            if (cls == 3) {
+                KMP_TRY(d.S.alloc(ts.size() * 4, "hipMalloc(dictionary tables)"));
+                HIP_TRY(hipMemcpy(d.S, ts.data(), ts.size() * 4, hipMemcpyHostToDevice));
+            }
             if (formatted) {
                 KMP_TRY(d.prior.alloc(sizeof(KDictPrior), "hipMalloc(dictionary entropy tables)"));
                 HIP_TRY(hipMemcpy(d.prior, &prior, sizeof(KDictPrior), hipMemcpyHostToDevice));
                 d.rep[0] = prior.rep[0]; d.rep[1] = prior.rep[1];
             } else { d.rep[0] = 1; d.rep[1] = 4; }
             d.content_size = content_size;
-            d.size = dict_size; d.hash = hsh;
+            d.size = dict_size; d.hash = hsh; d.level_class = cls;
             return KMP_OK;
         };
-        KMP_TRY(build_part(c->dict, KMP_PART_DICT, fill));
+        // (a build that fails -- memory is short -- leaves no dictionary behind: the ones the context kept go as well)
+        if (int const rc = build_part(c->dict[slot], KMP_PART_DICT, fill)) { for (auto& d : c->dict) d.reset(); return rc; }
     }
-    dict_part const& dp = *c->dict;
+    dict_part& dp = *c->dict[slot];
+    dp.used = ++c->dict_tick;
     KMP_TRY(batch_begin(c, st, d_in_len, n, c->max_slice_bytes));
     HIP_TRY(hipMemsetAsync(c->counter, 0, 4, st));
     KBatchView const v = batch_view(c, d_src, d_in_off, n, d_dst, d_out_off, d_out_len);
     KTeamTables flat; KMP_TRY(flat_tables(c, &flat));
-    KDictArgs const g = kx_dict_args(v, flat, c->counter, dp.content, dp.content_size, dp.L, dp.S, dp.W, dp.H, dp.C, dp.M, dp.rep[0], dp.rep[1]);
     u32 const tpw = 64 / (u32)c->G;
     u32 blocks = (n + tpw - 1) / tpw; if (blocks > c->match_blocks) blocks = c->match_blocks;
-    by_team_width(c->G, [&](auto w) { hipLaunchKernelGGL(k_zstd_match_dict<decltype(w)::value>, dim3(blocks), dim3(64), 0, st, g); });
+    u32 eflags = KXE_GATHER_LITS;                                 // literals are gathered by the entropy kernel
+    if (c->profiling) HIP_TRY(hipEventRecord(c->match[0].start, st));
+    if (cls == 3) {
+        KDictArgs const g = kx_dict_args(v, flat, c->counter, dp.content, dp.content_size, dp.L, dp.S, dp.W, dp.H, dp.C, dp.M, dp.rep[0], dp.rep[1]);
+        by_team_width(c->G, [&](auto w) { hipLaunchKernelGGL(k_zstd_match_dict<decltype(w)::value>, dim3(blocks), dim3(64), 0, st, g); });
+    } else {
+        KFastDictArgs const g = kx_fast_dict_args(v, flat, c->counter, dp.content, dp.content_size, dp.L, dp.W, dp.H, dp.M, dp.rep[0], dp.rep[1], level);
+        by_team_width(c->G, [&](auto w) { hipLaunchKernelGGL(k_zstd_match_fast_dict<decltype(w)::value>, dim3(blocks), dim3(64), 0, st, g); });
+        eflags = kx_entropy_flags_fast(level < 0);               // strategy "fast"; negative levels: literals stay raw
+    }
     HIP_TRY(hipGetLastError());
-    KEntropyArgs const e = kx_entropy_args(v, KXE_GATHER_LITS, dp.prior);       // literals are gathered by the entropy kernel
+    if (c->profiling) { HIP_TRY(hipEventRecord(c->match[0].end, st)); HIP_TRY(hipEventRecord(c->entropy[0].start, st)); }
+    KEntropyArgs const e = kx_entropy_args(v, eflags, dp.prior);
     if (dp.prior) hipLaunchKernelGGL(k_zstd_entropy_prior, dim3(n), dim3(64), 0, st, e);
     else hipLaunchKernelGGL(k_zstd_entropy, dim3(n), dim3(64), 0, st, e);
     HIP_TRY(hipGetLastError());
-    c->last_chunks = 1; c->zstd_timed = 0;
+    if (c->profiling) HIP_TRY(hipEventRecord(c->entropy[0].end, st));
+    c->last_chunks = 1; c->zstd_timed = c->profiling; c->timed_chunks = 1;      // (kmp_batch_last_kernel_ms: the parse and the entropy launch)
     return batch_end(c, st, d_in_len, n, c->max_slice_bytes, d_out_len, c->meta);
+}
+
+extern "C" int kmp_zstd_compress_batch_dict(kmp_batch_ctx* c, const void* d_src, const uint64_t* d_in_off, const uint32_t* d_in_len,
+                                            uint32_t n, void* d_dst, const uint64_t* d_out_off, uint32_t* d_out_len,
+                                            const void* h_dict, uint32_t dict_size, void* hip_stream)
+{ return zstd_compress_dict("kmp_zstd_compress_batch_dict", c, d_src, d_in_off, d_in_len, n, d_dst, d_out_off, d_out_len, h_dict, dict_size, 3, hip_stream); }
+
+extern "C" int kmp_zstd_compress_batch_dict_level(kmp_batch_ctx* c, const void* d_src, const uint64_t* d_in_off, const uint32_t* d_in_len,
+                                                  uint32_t n, void* d_dst, const uint64_t* d_out_off, uint32_t* d_out_len,
+                                                  const void* h_dict, uint32_t dict_size, int level, void* hip_stream)
+{
+    if (level == 0 || level == 3) return kmp_zstd_compress_batch_dict(c, d_src, d_in_off, d_in_len, n, d_dst, d_out_off, d_out_len, h_dict, dict_size, hip_stream);
+    if (level > 3 || level < -131072) { g_last_error = "kmp_zstd_compress_batch_dict_level: levels -131072 .. -1 and 1 .. 3 are served with a dictionary"; return KMP_ERR_ARG; }
+    return zstd_compress_dict("kmp_zstd_compress_batch_dict_level", c, d_src, d_in_off, d_in_len, n, d_dst, d_out_off, d_out_len, h_dict, dict_size, level, hip_stream);
 }
 
 // Slices above 128 KiB: frames of several blocks.  Every round runs the match kernel and the frame kernel over

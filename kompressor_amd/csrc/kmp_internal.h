@@ -123,10 +123,13 @@ struct lazy_big_part {
     dev_buf<u8> tables; dev_buf<KSeqPrev> prev; dev_buf<u32> small_len; u32 chunk = 0; u64 slot_bytes = 0;
     size_t bytes() const { return tables.bytes + prev.bytes + small_len.bytes; }
 };
-// the dictionary of the last kmp_zstd_compress_batch_dict call: content, CDict tables (built on the host), a formatted one's tables
+// a dictionary of the kmp_zstd_compress_batch_dict calls at one level class (kx_dict_level_class: the CDict's parameters and fill differ by
+// it): content, CDict tables (built on the host; strategy "fast" has L alone), a formatted one's tables.  A context keeps the last
+// KMP_DICT_SLOTS of them (used: the context's dict_tick when a batch last ran with it; the one unused longest makes room)
+enum { KMP_DICT_SLOTS = 4 };
 struct dict_part {
     dev_buf<u8> content; dev_buf<u32> L, S; dev_buf<KDictPrior> prior;
-    u32 size = 0, content_size = 0; u64 hash = 0; u32 W = 0, H = 0, C = 0, M = 0; u32 rep[2] = { 0, 0 };
+    u32 size = 0, content_size = 0; u64 hash = 0; u32 W = 0, H = 0, C = 0, M = 0; u32 rep[2] = { 0, 0 }; int level_class = 3; u64 used = 0;
     size_t bytes() const { return content.bytes + L.bytes + S.bytes + prior.bytes; }
 };
 // ... for the decoder: the caller's dictionary lies in device memory, its head is read back once per dictionary
@@ -186,7 +189,7 @@ struct kmp_batch_ctx {
     std::unique_ptr<table_part> flat, t4, chain_t4;
     std::unique_ptr<lazy_part> lz;
     std::unique_ptr<lazy_big_part> lzb;
-    std::unique_ptr<dict_part> dict;
+    std::unique_ptr<dict_part> dict[KMP_DICT_SLOTS]; u64 dict_tick = 0;
     std::unique_ptr<ddict_part> ddict;
     std::unique_ptr<pre_seq_part> pre_seq; std::unique_ptr<pre_lit_part> pre_lit;
     u32 pre_slices = 0, pre_blk_cap = 0; int pre_tried = 0;      // entries the staging holds (a larger batch is decoded in pieces); pre_tried: do not try again

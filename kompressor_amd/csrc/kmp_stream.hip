@@ -157,7 +157,6 @@ static size_t run_single_compress(kmp_zstd_cctx* c, size_t first_room, size_t en
                                                 : n <= KMP_MAX_SLICE_BYTES ? !(c->level >= 9 && n <= 16384u) : (in_place && n <= KX_LAZY_BIG_MAX));
         if (!served) return KERRC(ZE_parameter_unsupported);
     }
-    if (c->level < 0 && !c->dict.empty()) return KERRC(ZE_parameter_unsupported);
     // the plain case -- level 3, no dictionary, the whole slice at once, one block -- joins whatever other contexts are
     // closing right now: one batch for all of them (kmp_coalesce.h); the frame is the one this context would get alone
     if (!streaming && c->level == 3 && c->dict.empty() && n <= KMP_MAX_SLICE_BYTES && coalesce_enabled()) {
@@ -187,14 +186,14 @@ static size_t run_single_compress(kmp_zstd_cctx* c, size_t first_room, size_t en
         // the reference's one-shot driver above 128 KiB: staged input
         if (kmp_zstd_compress_batch_reference(s.batch.get(), s.d_in, s.d_off, s.d_len, 1, s.d_out, s.d_off + 1, s.d_len + 1, c->level, (u32)first_room, nullptr) != KMP_OK) return KERRC(ZE_GENERIC);
     } else
-    if (c->level != 3) {
-        if (!c->dict.empty()) return KERRC(ZE_parameter_unsupported);   // levels 1 / 2: no dictionary
+    if (c->level != 3 && c->dict.empty()) {
         if (kmp_zstd_compress_batch_level(s.batch.get(), s.d_in, s.d_off, s.d_len, 1, s.d_out, s.d_off + 1, s.d_len + 1, c->level, nullptr) != KMP_OK) return KERRC(ZE_GENERIC);
     } else
     if (!c->dict.empty()) {
-        if (n > KMP_MAX_SLICE_BYTES) return KERRC(ZE_srcSize_wrong);          // frames of several blocks with a dictionary: CPU library
-        if (kmp_zstd_compress_batch_dict(s.batch.get(), s.d_in, s.d_off, s.d_len, 1, s.d_out, s.d_off + 1, s.d_len + 1,
-                                         c->dict.data(), (u32)c->dict.size(), nullptr) != KMP_OK) {
+        // frames of several blocks with a dictionary: CPU library (the code each level had before levels 1, 2 and the negative ones took dictionaries)
+        if (n > KMP_MAX_SLICE_BYTES) return c->level == 3 ? KERRC(ZE_srcSize_wrong) : KERRC(ZE_parameter_unsupported);
+        if (kmp_zstd_compress_batch_dict_level(s.batch.get(), s.d_in, s.d_off, s.d_len, 1, s.d_out, s.d_off + 1, s.d_len + 1,
+                                               c->dict.data(), (u32)c->dict.size(), c->level, nullptr) != KMP_OK) {
             return dict_header_state(c->dict.data(), c->dict.size(), 0) < 0 ? KERRC(ZE_dictionary_corrupted) : KERRC(ZE_GENERIC);
         }
     } else

@@ -1,19 +1,32 @@
-// zstd_cdict_host.h -- host-side construction of libzstd's CDict for a raw-content dictionary at level 3:
-// parameters of ZSTD_getCParams(3, unknown source size, dictSize) in "create CDict" mode, then
-// ZSTD_fillDoubleHashTableForCDict over the dictionary (tagged entries: index << 8 | tag, index = position + 2).
-// Built once per dictionary on the host and uploaded (kmp_batch.hip: kmp_zstd_compress_batch_dict); the emulator harness uses the same code.
+// zstd_cdict_host.h -- host-side construction of libzstd's CDict for a dictionary's content: parameters of
+// ZSTD_getCParams(level, unknown source size, dictSize) in "create CDict" mode, then the fill of its tables over the dictionary
+// (tagged entries: index << 8 | tag, index = position + 2): ZSTD_fillDoubleHashTableForCDict at level 3 (strategy "double-fast"),
+// ZSTD_fillHashTableForCDict at levels 1, 2 and the negative ones (strategy "fast", one table).
+// Built once per dictionary and level class on the host and uploaded (kmp_batch.hip: kmp_zstd_compress_batch_dict_level); the emulator harness uses the same code.
 #pragma once
 #include <stdint.h>
 #include <string.h>
 #include <vector>
 static inline u32 hb32_host(u32 v) { return 31u - (u32)__builtin_clz(v); }
-static inline void cdict_params(u32 dictSize, u32* W, u32* C, u32* H, u32* mml)
+// level: 3 (or 0), 1, 2, or a negative level (row 0 of libzstd's tables; its targetLength = -level does not size anything).  With
+// dictionaries of at most KX_MAX_DICT bytes the rows of levels 1, 2 and 0 are all strategy "fast" (C: their chainLog, which no table has)
+static inline void cdict_params(u32 dictSize, u32* W, u32* C, u32* H, u32* mml, int level = 3)
 {
-    u64 const rSize = (u64)dictSize + 500;
-    if (rSize <= 16384)       { *W = 14; *C = 14; *H = 15; *mml = 4; }
-    else if (rSize <= 131072) { *W = 17; *C = 15; *H = 16; *mml = 5; }
-    else if (rSize <= 262144) { *W = 18; *C = 16; *H = 16; *mml = 4; }
-    else                      { *W = 21; *C = 16; *H = 17; *mml = 5; }
+    if (level == 3 || level == 0) {
+        u64 const rSize = (u64)dictSize + 500;
+        if (rSize <= 16384)       { *W = 14; *C = 14; *H = 15; *mml = 4; }
+        else if (rSize <= 131072) { *W = 17; *C = 15; *H = 16; *mml = 5; }
+        else if (rSize <= 262144) { *W = 18; *C = 16; *H = 16; *mml = 4; }
+        else                      { *W = 21; *C = 16; *H = 17; *mml = 5; }
+    } else {
+        // libzstd adds the dictionary's size and 500 to the unknown source size, which is (u64)-1: the sum wraps to dictSize + 499, and
+        // the binary library changes rows between 15 885 and 15 886 bytes.  (The level-3 rows above keep the + 500 they were written
+        // with: a dictionary of exactly 15 885 bytes gets the larger row there, one byte early.)
+        bool const small = (u64)dictSize + 499 <= 16384;
+        if (level == 1)      { if (small) { *W = 14; *C = 14; *H = 15; *mml = 5; } else { *W = 17; *C = 12; *H = 13; *mml = 6; } }
+        else if (level == 2) { if (small) { *W = 14; *C = 14; *H = 15; *mml = 4; } else { *W = 17; *C = 13; *H = 15; *mml = 5; } }
+        else                 { if (small) { *W = 14; *C = 12; *H = 13; *mml = 5; } else { *W = 17; *C = 12; *H = 12; *mml = 5; } }
+    }
     u32 const srcSize = 513, tSize = srcSize + dictSize;
     u32 const srcLog = (tSize < 64) ? 6 : hb32_host(tSize - 1) + 1;
     if (*W > srcLog) *W = srcLog;
@@ -43,6 +56,28 @@ static inline void cdict_fill(std::vector<u32>& tl, u32 hLog, std::vector<u32>& 
             u32 const sm = hash_short_host(ip + i, cLog + 8, mls), lg = hash_long_host(ip + i, hLog + 8);
             if (i == 0) ts[sm >> 8] = ((curr + i) << 8) | (sm & 0xFFu);
             if (i == 0 || tl[lg >> 8] == 0) tl[lg >> 8] = ((curr + i) << 8) | (lg & 0xFFu);
+        }
+    }
+}
+// ... of strategy "fast": minMatch 4 .. 6, one table (ZSTD_fillHashTableForCDict: every third position, the two between only into
+// empty cells); C: the row's chainLog, which only takes part in the cut-off for large dictionaries
+static inline u32 hash_any_host(const u8* p, u32 hBits, u32 mls)
+{
+    if (mls <= 5) return hash_short_host(p, hBits, mls);
+    return (u32)(((rd64_host(p) << 16) * 227718039650203ULL) >> (64 - hBits));
+}
+static inline void cdict_fill_fast(std::vector<u32>& t, u32 hLog, u32 cLog, u32 mls, const u8* dict, size_t D)
+{
+    t.assign((size_t)1 << hLog, 0u);
+    size_t const maxDict = (size_t)1 << ((hLog + 3 > cLog + 1) ? hLog + 3 : cLog + 1);
+    size_t const from = D > maxDict ? D - maxDict : 0;
+    if (D - from <= 8) return;
+    const u8* ip = dict + from; const u8* const iend = dict + D - 8;
+    for (; ip + 2 <= iend; ip += 3) {
+        u32 const curr = 2u + (u32)(ip - dict);
+        for (u32 i = 0; i < 3; ++i) {
+            u32 const h = hash_any_host(ip + i, hLog + 8, mls);
+            if (i == 0 || t[h >> 8] == 0) t[h >> 8] = ((curr + i) << 8) | (h & 0xFFu);
         }
     }
 }

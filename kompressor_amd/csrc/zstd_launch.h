@@ -4,6 +4,7 @@
 #pragma once
 #include "zstd_entropy.h"           // (brings zstd_match.h, zstd_match_ext.h, zstd_match_fast.h)
 #include "zstd_match_dict.h"
+#include "zstd_match_fast_dict.h"
 #include "zstd_lazy.h"
 #include "zstd_lazy_big.h"
 #include <type_traits>
@@ -87,6 +88,19 @@ inline KDictArgs kx_dict_args(KBatchView const& v, KTeamTables const& t, u32* co
     g.dWindowLog = W; g.dHashLog = H; g.dChainLog = C; g.dMinMatch = M;
     return g;
 }
+// ... at levels 1, 2 and the negative ones (strategy "fast": one CDict table H with the parameters W, Hlog, M of the level's row)
+inline KFastDictArgs kx_fast_dict_args(KBatchView const& v, KTeamTables const& t, u32* counter, const u8* content, u32 content_size,
+                                       const u32* H, u32 W, u32 Hlog, u32 M, u32 rep0, u32 rep1, int level)
+{
+    KFastDictArgs g;
+    g.m = kx_match_args(v, t, counter, KXM_NT_STORES | KXM_NO_LITS);
+    g.dict = content; g.dict_size = content_size; g.dictH = H; g.rep0 = rep0; g.rep1 = rep1;
+    g.dWindowLog = W; g.dHashLog = Hlog; g.dMinMatch = M;
+    g.step = level < 0 ? (u32)(-level) : 1u;             // targetLength + !targetLength
+    return g;
+}
+// which CDict a level asks for: 3 (and 0) double-fast, 1, 2, or -1 for every negative level (row 0; the step is no part of the tables)
+inline int kx_dict_level_class(int level) { return level < 0 ? -1 : level == 0 ? 3 : level; }
 // levels 5 .. 10 (and level 4's slices up to 16 KiB): rec / wr hold pos_cap positions for each of the view's slices
 inline KLazyArgs kx_lazy_args(KBatchView const& v, KLazyRec* rec, u32* wr, u32 pos_cap, int level)
 {

@@ -27,6 +27,11 @@ def _buf(ba):
 
 
 class ZstdCompressor(SliceTransform):
+    """ZstdCompressor(compressionLevel, dictionary) of the reference: ZSTD_CCtx_setParameter + ZSTD_CCtx_loadDictionary, then frames through
+    kmp_zstd_compress_stream.  With a dictionary (raw content or zstd's own format, 8 .. 130 560 bytes) levels 1, 2, 3 and the negative
+    ones are served for what arrives in one closing call of at most 128 KiB; levels 4 .. 10, larger slices and input that arrived with
+    finish = false are refused with a dictionary ("Unsupported parameter") when the stream closes."""
+
     def __init__(self, compression_level=3, dictionary=None):
         lib = self._lib = _lib.load()
         self._cctx = lib.kmp_zstd_create_cctx()
