@@ -315,7 +315,8 @@ KMP_API int kmp_zstd_compress_batch_dict_level(kmp_batch_ctx* ctx,
  * 14 = unsupported frame parameter ...).  An entry may hold several frames back to back, with skippable frames
  * between them: their contents are concatenated, as ZSTD_decompress does; an empty entry decodes to nothing.
  * Nothing outside [d_in_off[i], +d_in_len[i]) is read and nothing outside [d_out_off[i], +d_out_cap[i]) is
- * written, whatever the bytes of the entry are (tests/fuzz_decoders.py). */
+ * written, whatever the bytes of the entry are (tests/fuzz_decoders.py).  A caller that does not know the sizes gets d_out_cap and
+ * d_out_off from kmp_zstd_frame_info_batch + kmp_batch_layout below. */
 KMP_API int kmp_zstd_decompress_batch(kmp_batch_ctx* ctx,
                                       const void* d_src, const uint64_t* d_in_off, const uint32_t* d_in_len,
                                       uint32_t n,
@@ -334,6 +335,45 @@ KMP_API int kmp_zstd_decompress_batch_dict(kmp_batch_ctx* ctx,
                                            uint32_t* d_out_len, uint32_t* d_status,
                                            const void* d_dict, uint32_t dict_size,
                                            void* hip_stream);
+
+/* What the entries of a batch declare about themselves, without decoding them: the batched form of libzstd's ZSTD_findDecompressedSize,
+ * ZSTD_decompressBound and ZSTD_findFrameCompressedSize, for callers whose frames lie in device memory and whose sizes did not travel
+ * with them.  Entry i is d_src[d_in_off[i] .. +d_in_len[i]), walked frame by frame as ZSTD_decompressBound walks it: skippable frames
+ * (magic 0x184D2A5?), zstd frames header by header and block header by block header; nothing is decoded and no byte outside the entry
+ * is read, whatever its bytes and wherever it lies.  The answers are libzstd 1.5.7's, damaged and short entries included
+ * (tests/golden/zstd_frame_info_golden.json).  An empty entry is content 0, bound 0, status 0, frames 0. */
+#define KMP_CONTENT_UNKNOWN (~0ull)
+typedef struct {
+    uint64_t content;   /* ZSTD_findDecompressedSize of the entry: the exact total, or KMP_CONTENT_UNKNOWN when a frame declares none
+                         * (~0ull - 1, the library's ZSTD_CONTENTSIZE_ERROR, when the total of the declared sizes wraps 64 bits) */
+    uint64_t bound;     /* ZSTD_decompressBound of the entry: declared size where there is one, else blocks x min(window, 128 KiB), summed */
+    uint32_t status;    /* 0, or libzstd's error code for the first frame that ZSTD_findFrameCompressedSize rejects: 10 no known magic,
+                         * 14 reserved bit / skippable size that wraps, 16 window above 2^31, 20 reserved block type, 72 the entry ends
+                         * inside a header, a block or a checksum.  Then content and bound are 0. */
+    uint32_t frames;    /* zstd frames in the entry (skippable ones not counted; with a status: those in front of the rejected one) */
+    uint32_t dict_id;   /* the first zstd frame's dictionary ID, 0 = none */
+    uint32_t flags;     /* bit 0: some frame carries a checksum; bit 1: the entry holds a skippable frame; bit 2: it holds a frame in the
+                         * format of zstd 0.5, 0.6 or 0.7 (magic 0xFD2FB525 .. 27), which a libzstd built with legacy support -- the
+                         * binary 1.5.7 is -- sizes like any other and which is counted in `frames`; the decoders here answer 10 for it */
+} kmp_zstd_frame_info;  /* 32 bytes */
+/* d_info[i] (device memory of the caller's, n entries, 8-byte aligned) receives entry i's answers: one kernel, a lane per entry,
+ * asynchronous on hip_stream -- no allocation, no host wait, nothing of the context's decode staging is touched (a context that has
+ * never decoded stays as small as it was).  n up to the context's max_slices; n == 0 is KMP_OK. */
+KMP_API int kmp_zstd_frame_info_batch(kmp_batch_ctx* ctx, const void* d_src, const uint64_t* d_in_off, const uint32_t* d_in_len, uint32_t n,
+                                      kmp_zstd_frame_info* d_info, void* hip_stream);
+/* The layout of a decode made of those answers, on the device: d_out_cap[i] = bound[i] -- or 0 where status[i] != 0 or the bound does
+ * not fit the ABI's 32-bit capacities (the decoder then reports the entry itself: its own error for a damaged one, 70 for one too
+ * large) --, d_out_off[i] = the sum of the capacities in front of it, each rounded up to `align` (a power of two from 1 to 4096, else
+ * KMP_ERR_ARG), d_total[0] = the sum over all n: what the destination must hold, d_total[1] = the entries given capacity 0 for one of
+ * the two reasons.  One kernel, asynchronous, deterministic; the arrays are what kmp_zstd_decompress_batch takes.  A caller reads
+ * d_total[0] back once (the one host wait, forced by the allocation), or decodes into a destination it knows to be large enough
+ * without any. */
+KMP_API int kmp_batch_layout(kmp_batch_ctx* ctx, const kmp_zstd_frame_info* d_info, uint32_t n, uint32_t align,
+                             uint64_t* d_out_off, uint32_t* d_out_cap, uint64_t* d_total /* [2] */, void* hip_stream);
+/* The same inspection of entries in HOST memory: the same code compiled for the host, no GPU touched, no context needed (a batch of
+ * 8 192 entries or more is spread over up to 16 threads). */
+KMP_API int kmp_zstd_frame_info_host(const void* h_src, const uint64_t* in_off, const uint32_t* in_len, uint32_t n,
+                                     kmp_zstd_frame_info* info);
 
 /* Raw DEFLATE (RFC 1951) streams as zlib level 6 / windowBits 15 / memLevel 8 / strategy 0 writes
  * them: the batched form of deflateInit2(6, Z_DEFLATED, -15, 8, 0) + deflate(Z_FINISH)

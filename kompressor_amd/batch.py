@@ -39,11 +39,42 @@ def compress_host_batch(slices, level=3, device=0):
     return [dst[int(ooff[i]):int(ooff[i]) + int(olen[i])].tobytes() for i in range(n)]
 
 
-def decompress_host_batch(frames, caps, device=0):
-    """kmp_zstd_decompress_host_batch: frames in host memory -> (contents, statuses); caps[i] = room for entry i (<= 128 KiB)."""
+def frame_info_host(frames):
+    """kmp_zstd_frame_info_host: what each entry's frames declare (ZSTD_findDecompressedSize, ZSTD_decompressBound, the first error
+    of ZSTD_findFrameCompressedSize), parsed on the host, no GPU touched.  -> a numpy structured array with the fields of
+    kmp_zstd_frame_info: content, bound, status, frames, dict_id, flags."""
     import numpy as np
     lib = _lib.load()
     n = len(frames)
+    lens = np.array([len(f) for f in frames], dtype=np.uint32)
+    offs = np.zeros(n, dtype=np.uint64)
+    if n > 1:
+        offs[1:] = np.cumsum(lens[:-1], dtype=np.uint64)
+    src = np.frombuffer(b"".join(bytes(f) for f in frames) + b"\0", dtype=np.uint8)
+    info = np.zeros(n, dtype=np.dtype([("content", "<u8"), ("bound", "<u8"), ("status", "<u4"), ("frames", "<u4"), ("dict_id", "<u4"), ("flags", "<u4")]))
+    p = lambda a: ctypes.c_void_p(a.ctypes.data)          # noqa: E731
+    rc = lib.kmp_zstd_frame_info_host(p(src), p(offs), p(lens), n, p(info))
+    if rc != 0:
+        raise RuntimeError(f"kmp_zstd_frame_info_host failed ({rc}): {_lib.last_error()}")
+    return info
+
+
+def decompress_host_batch(frames, caps=None, device=0):
+    """kmp_zstd_decompress_host_batch: frames in host memory -> (contents, statuses); caps[i] = room for entry i (<= 128 KiB).
+    caps=None: the room is each entry's bound, read off its frames (frame_info_host); an entry that fails the inspection raises
+    RuntimeError with libzstd's name for the error."""
+    import numpy as np
+    lib = _lib.load()
+    n = len(frames)
+    if caps is None:
+        info = frame_info_host(frames)
+        for i in range(n):
+            if info["status"][i]:
+                name = lib.kmp_zstd_get_error_name((1 << 64) - int(info["status"][i])).decode()
+                raise RuntimeError(f"decompress_host_batch: entry {i} of {n}: {name}")
+        if n and int(info["bound"].max()) >= (1 << 32):
+            raise RuntimeError("decompress_host_batch: an entry's bound is 4 GiB or more")
+        caps = info["bound"]
     lens = np.array([len(f) for f in frames], dtype=np.uint32)
     offs = np.zeros(n, dtype=np.uint64)
     if n > 1:
@@ -239,10 +270,53 @@ class ZstdBatch:
         if rc != 0:
             raise RuntimeError(f"kmp_compact_batch failed ({rc}): {self._err()}")
 
-    def decompress(self, src, in_off, in_len, out_cap, dst=None, out_off=None, dictionary=None):
-        """Frames -> slices.  out_cap: int32 device tensor of per-frame capacities.  dictionary: uint8 device tensor
-        with a raw-content dictionary shared by all frames.  Returns (dst, out_off, out_len, status)."""
+    def _frame_info_raw(self, src, in_off, in_len):
+        """kmp_zstd_frame_info_batch -> the n x 32 bytes of kmp_zstd_frame_info as an int64 tensor of n x 4 (queued, no host wait)"""
         n = in_len.numel()
+        info = torch.empty((n, 4), dtype=torch.int64, device=self.device)
+        rc = self.lib.kmp_zstd_frame_info_batch(self._h, _ptr(src), _ptr(in_off), _ptr(in_len), n, _ptr(info), self._stream())
+        if rc != 0:
+            raise RuntimeError(f"kmp_zstd_frame_info_batch failed ({rc}): {self._err()}")
+        return info
+
+    def frame_info(self, src, in_off, in_len):
+        """What each entry's frames declare, read on the device without decoding (kmp_zstd_frame_info_batch: the batched
+        ZSTD_findDecompressedSize / ZSTD_decompressBound / ZSTD_findFrameCompressedSize; no host wait).  Returns a dict of device
+        tensors over the n entries (views of one buffer): content and bound (int64; an unknown content size, ~0 in C, reads -1),
+        status (0 or libzstd's error code: then content and bound are 0), frames, dict_id, flags (int32; bit 0 a checksum, bit 1 a
+        skippable frame, bit 2 a frame in a format of zstd 0.5 .. 0.7)."""
+        info = self._frame_info_raw(src, in_off, in_len)
+        w = info.view(torch.int32)                      # n x 8 words
+        return {"content": info[:, 0], "bound": info[:, 1], "status": w[:, 4], "frames": w[:, 5], "dict_id": w[:, 6], "flags": w[:, 7]}
+
+    def layout(self, info, align=1):
+        """kmp_batch_layout over the tensor _frame_info_raw returns: (out_off int64, out_cap int32, total int64[2]) on the device, no
+        host wait: capacities = bounds (0 for a rejected entry or a bound of 4 GiB and more), offsets = their running sum with each
+        rounded up to align, total[0] = the bytes a destination needs, total[1] = the entries given capacity 0 for those reasons."""
+        n = info.shape[0]
+        out_off = torch.empty(n, dtype=torch.int64, device=self.device)
+        out_cap = torch.empty(n, dtype=torch.int32, device=self.device)
+        total = torch.empty(2, dtype=torch.int64, device=self.device)
+        rc = self.lib.kmp_batch_layout(self._h, _ptr(info), n, align, _ptr(out_off), _ptr(out_cap), _ptr(total), self._stream())
+        if rc != 0:
+            raise RuntimeError(f"kmp_batch_layout failed ({rc}): {self._err()}")
+        return out_off, out_cap, total
+
+    def decompress(self, src, in_off, in_len, out_cap=None, dst=None, out_off=None, dictionary=None, align=1):
+        """Frames -> slices.  out_cap: int32 device tensor of per-frame capacities.  dictionary: uint8 device tensor
+        with a raw-content dictionary shared by all frames.  Returns (dst, out_off, out_len, status).
+        out_cap=None: the sizes are read off the frames on the device (frame_info, then layout with `align`: a power of two up to
+        4096 that every out_off is a multiple of); the one host wait is reading the total back to allocate dst.  An entry whose
+        inspection fails (or whose bound is 4 GiB or more) gets capacity 0, and the decoder's own status for it is nonzero.
+        Frames without a declared size get their bound: blocks x min(window, 128 KiB)."""
+        n = in_len.numel()
+        if out_cap is None:
+            if dst is not None or out_off is not None:
+                raise ValueError("out_cap=None lays the destination out itself: pass neither dst nor out_off")
+            out_off, out_cap, total = self.layout(self._frame_info_raw(src, in_off, in_len), align)
+            dst = torch.empty(int(total[0].item()) + 64, dtype=torch.uint8, device=self.device)
+        elif align != 1:
+            raise ValueError("align belongs to out_cap=None (with out_cap given, out_off is the caller's)")
         if out_off is None:
             out_off = torch.cumsum(out_cap.to(torch.int64), 0) - out_cap.to(torch.int64)
         if dst is None:

@@ -10,11 +10,13 @@
 #include "zstd_cdict_host.h"
 #include "zstd_decode.h"
 #include "zstd_predecode.h"
+#include "zstd_frame_info.h"         // (frame inspection and the decode layout made of it)
 #include "deflate_match.h"          // (KdBest & co.: the context frees the DEFLATE workspace)
 #include "kmp_internal.h"
 
 #include <mutex>
 #include <new>
+#include <thread>
 #include <vector>
 
 // --------------------------------------------------------------------------
@@ -127,6 +129,9 @@ __global__ __launch_bounds__(64) void k_zstd_lit_predecode(KLitArgs a) { zstd_li
 __global__ __launch_bounds__(256) void k_zstd_seq_count(KSeqSortArgs a) { zstd_seq_count_body(a); }
 __global__ __launch_bounds__(256) void k_zstd_seq_rank(KSeqSortArgs a) { zstd_seq_rank_body(a); }
 __global__ __launch_bounds__(256) void k_zstd_seq_perm(KSeqSortArgs a) { zstd_seq_perm_body(a); }
+// what each entry's frames declare, a lane per entry; capacities and offsets of a decode made of it, one workgroup
+__global__ __launch_bounds__(256) void k_zstd_frame_info(KFrameInfoArgs a) { zstd_frame_info_body(a); }
+__global__ __launch_bounds__(64 * KFI_LAYOUT_WAVES) void k_batch_layout(KLayoutArgs a) { batch_layout_body(a); }
 // exclusive prefix sum of u32 lengths into u64 offsets, single workgroup
 __global__ __launch_bounds__(1024) void k_scan_lengths(const u32* len, u32 n, u64* off)
 {
@@ -1494,6 +1499,47 @@ extern "C" int kmp_zstd_decompress_batch_dict(kmp_batch_ctx* c, const void* d_sr
                                               uint32_t n, void* d_dst, const uint64_t* d_out_off, const uint32_t* d_out_cap,
                                               uint32_t* d_out_len, uint32_t* d_status, const void* d_dict, uint32_t dict_size, void* hip_stream)
 { return zstd_decompress_impl(c, d_src, d_in_off, d_in_len, n, d_dst, d_out_off, d_out_cap, d_out_len, d_status, d_dict, dict_size, hip_stream); }
+// Frame inspection: neither call allocates, waits or touches the context's decode staging; they are queued on the caller's stream
+// like any kernel of its own (no batch_begin: nothing of the context is used but its device and max_slices).
+extern "C" int kmp_zstd_frame_info_batch(kmp_batch_ctx* c, const void* d_src, const uint64_t* d_in_off, const uint32_t* d_in_len, uint32_t n,
+                                         kmp_zstd_frame_info* d_info, void* hip_stream)
+{
+    KMP_TRY(batch_args("kmp_zstd_frame_info_batch", c, n, { d_src, d_in_off, d_in_len, d_info }));
+    if (n == 0) return KMP_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    KFrameInfoArgs const a = { (const u8*)d_src, d_in_off, d_in_len, n, d_info };
+    u32 const blocks = (n + 255u) / 256u;                    // (n is bounded by max_slices; the body strides over what a smaller grid leaves)
+    hipLaunchKernelGGL(k_zstd_frame_info, dim3(blocks < 4096u ? blocks : 4096u), dim3(256), 0, (hipStream_t)hip_stream, a);
+    HIP_TRY(hipGetLastError());
+    return KMP_OK;
+}
+extern "C" int kmp_batch_layout(kmp_batch_ctx* c, const kmp_zstd_frame_info* d_info, uint32_t n, uint32_t align,
+                                uint64_t* d_out_off, uint32_t* d_out_cap, uint64_t* d_total, void* hip_stream)
+{
+    KMP_TRY(batch_args("kmp_batch_layout", c, n, { d_info, d_out_off, d_out_cap, d_total }));
+    if (align == 0 || align > 4096u || (align & (align - 1u))) { g_last_error = "kmp_batch_layout: align must be a power of two from 1 to 4096"; return KMP_ERR_ARG; }
+    HIP_TRY(hipSetDevice(c->device));
+    if (n == 0) { if (d_total) HIP_TRY(hipMemsetAsync(d_total, 0, 2 * sizeof(uint64_t), (hipStream_t)hip_stream)); return KMP_OK; }
+    KLayoutArgs const a = { d_info, n, align, d_out_off, d_out_cap, d_total };
+    hipLaunchKernelGGL(k_batch_layout, dim3(1), dim3(64 * KFI_LAYOUT_WAVES), 0, (hipStream_t)hip_stream, a);
+    HIP_TRY(hipGetLastError());
+    return KMP_OK;
+}
+// ... and on the host: the same body through the compiler's host pass, no GPU touched; large batches on up to 16 threads
+extern "C" int kmp_zstd_frame_info_host(const void* h_src, const uint64_t* in_off, const uint32_t* in_len, uint32_t n, kmp_zstd_frame_info* info)
+{
+    KMP_TRY(args_present("kmp_zstd_frame_info_host", true, n, { h_src, in_off, in_len, info }));
+    auto run = [=](u32 b, u32 e) { for (u32 i = b; i < e; i++) kx_frame_info((const u8*)h_src + in_off[i], in_len[i], info + i); };
+    u32 hw = std::thread::hardware_concurrency();
+    u32 const workers = n < 8192u ? 1u : hw < 2u ? 1u : hw > 16u ? 16u : hw;
+    if (workers == 1u) { run(0, n); return KMP_OK; }
+    std::vector<std::thread> th;
+    u32 const per = (n + workers - 1u) / workers;
+    for (u32 b = per; b < n; b += per) th.emplace_back(run, b, n - b < per ? n : b + per);
+    run(0, per);
+    for (auto& t : th) t.join();
+    return KMP_OK;
+}
 extern "C" int kmp_compact_batch(kmp_batch_ctx* c, const void* d_src, const uint64_t* d_in_off, const uint32_t* d_len, uint32_t n,
                                  void* d_dst, uint64_t* d_out_off, void* hip_stream)
 {
