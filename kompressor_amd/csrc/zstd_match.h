@@ -21,6 +21,7 @@
 // All cross-lane primitives are called from wave-uniform control flow.
 #pragma once
 #include "zstd_common.h"
+#include "zstd_team.h"
 
 struct KMatchArgs {
     const u8* src; const u64* in_off; const u32* in_len; u32 n_slices;
@@ -155,7 +156,6 @@ struct KNoDone { static constexpr bool on = false; KX_MEMBER void operator()(u32
 template <int G, bool BLK = false, class DONE = KNoDone>
 KX_DEV void zstd_match_body(const KMatchArgs& a, DONE const& done = DONE())
 {
-    constexpr int NT = 64 / G;
     bool const wide = BLK && (a.flags & KXM_WIDE);               // entries without check bits (indices need all 32 bits)
     u32 const IDXM = BLK ? (wide ? 0xFFFFFFFFu : KX_BLK_IDX_MASK) : KX_IDX_MASK;
     constexpr u32 TAGM = BLK ? 0u : KX_TAG_MASK;            // block mode: no epoch (tag stays 0)
@@ -163,26 +163,20 @@ KX_DEV void zstd_match_body(const KMatchArgs& a, DONE const& done = DONE())
     u32 const CHKM = BLK ? (wide ? 0u : KX_BLK_CHK_MASK) : KX_CHK_MASK;
     // lowest valid index (position + 2) of the running block: 2 unless the window has slid (block mode, long slices)
     u32 lowIdx = 2u;
-    int const lane = kx_lane();
-    int const k = lane & (G - 1);
-    int const tbase = lane - k;
-    u32 const team = (kx_block() + a.block_base) * NT + (u32)(lane / G);
+    auto const [lane, k, tbase, tmask, team] = kx_team<G>(a.block_base);
     u32* L = BLK ? a.big_tables : kx_team_tables(a, team);
     u32* S = L + (BLK ? a.big_long : a.tbl_long);
     int bstart = 0; u32 saved1 = 0, saved2 = 0;          // block mode: block start, repcodes set aside at block start
-    u64 const tmask = (G == 64) ? ~0ull : ((1ull << G) - 1ull);
 
     // ---- team state (uniform across the team's lanes) -------------------
     int state = KST_IDLE;
     const u8* src = a.src; int n = 0; int ilimit = 0; u32 slice = 0;
     int ip = 0, anchor = 0; u32 off1 = 0, off2 = 0; int step = 1; int nextStep = 0;
-    u32 nseq = 0, nlit = 0; u32 tag = 0; u32 hbL = 16, hbS = 15, mls = 5;
-    u32 longType = 0, longPos = 0; u32 guard = 0; u32 status = 0;
-    KSeq* seqs = a.seqs; u8* lits = a.lits;
+    u32 tag = 0; u32 hbL = 16, hbS = 15, mls = 5;
+    u32 guard = 0; u32 status = 0;
+    KSeqSink sink = { a.seqs }; u8* lits = a.lits;
     // pending match
     int m_type = 0, m_pos = 0, m_start = 0, m_mpos = 0; u32 m_len0 = 0, m_off = 0, m_idxl1 = 0; u64 m_w1 = 0;
-    // sequences wait in registers (two per lane) until the team can store whole 16-byte pieces of a line
-    u64 sq0 = 0, sq1 = 0;
     // long-table lookup of the first position of the next step, when the last step's extra lane already made it
     bool carry = false; u32 carry_idxl = 0;
     // KXM_ADAPTIVE (experiment): the speculation width follows the last hit -- after a hit at lane w the next step looks at
@@ -198,16 +192,8 @@ KX_DEV void zstd_match_body(const KMatchArgs& a, DONE const& done = DONE())
     for (;;) {
         // ================= fetch the next slice =======================
         if (kx_any(state == KST_IDLE)) {
-            u32 s = 0, ep = 0;
-            if (state == KST_IDLE && k == 0) {
-                s = kx_atomic_add(a.counter, 1u);
-                if (!BLK && s < a.n_slices) {
-                    ep = a.team_epoch[team] + 1;
-                    if (ep > KX_EPOCH_MAX) ep = 0;          // 0 = "clear the tables, restart at 1"
-                    a.team_epoch[team] = ep ? ep : 1u;
-                }
-            }
-            s = kx_shfl(s, tbase); ep = kx_shfl(ep, tbase);
+            KClaim const cl = kx_team_claim<!BLK>(state == KST_IDLE && k == 0, tbase, a.counter, a.n_slices, a.team_epoch + team);
+            u32 const s = cl.s;
             if (state == KST_IDLE) {
                 if (s >= a.n_slices) state = KST_DONE;
                 else if (BLK) {
@@ -220,11 +206,11 @@ KX_DEV void zstd_match_body(const KMatchArgs& a, DONE const& done = DONE())
                     if (fs.blockSize != 0 && !bw.ext && kx_in_class((a.flags >> KXM_CLASS_SHIFT) & KXM_CLASS_MASK, a.in_len[s])) {           // else: frame finished (or not this launch's), fetch the next slice
                         slice = s;
                         src = a.src + a.in_off[s];
-                        seqs = a.seqs + (size_t)s * a.seq_cap; lits = a.lits + (size_t)s * a.lit_cap;
+                        sink.reset(a.seqs + (size_t)s * a.seq_cap); lits = a.lits + (size_t)s * a.lit_cap;
                         L = a.big_tables + (size_t)s * a.big_stride; S = L + a.big_long;
                         KParams const P = P0;
                         hbL = P.hashLog; hbS = P.chainLog; mls = P.minMatch;
-                        nseq = 0; nlit = 0; longType = 0; longPos = 0; guard = 0; status = 0; tag = 0;
+                        guard = 0; status = 0; tag = 0;
                         bstart = (int)fs.ipos; n = bstart + (int)fs.blockSize;       // n = end of the block
                         anchor = bstart; ilimit = n - 8;
                         // candidates: valid from ZSTD_getLowestPrefixIndex at the block's END on ...
@@ -243,16 +229,12 @@ KX_DEV void zstd_match_body(const KMatchArgs& a, DONE const& done = DONE())
                     slice = s;
                     src = a.src + a.in_off[s];
                     n = (int)a.in_len[s];
-                    seqs = a.seqs + (size_t)s * a.seq_cap; lits = a.lits + (size_t)s * a.lit_cap;
+                    sink.reset(a.seqs + (size_t)s * a.seq_cap); lits = a.lits + (size_t)s * a.lit_cap;
                     bool lvl_ok = true;
                     KParams const P = (a.level == 4u) ? kx_params_l4((u32)n, lvl_ok) : kx_params_l3((u32)n);
                     hbL = P.hashLog; hbS = P.chainLog; mls = P.minMatch;
-                    nseq = 0; nlit = 0; longType = 0; longPos = 0; guard = 0; status = lvl_ok ? 0u : 3u;      // 3: no double-fast row for this size at this level
-                    if (ep == 0) {
-                        for (u32 i = (u32)k; i < a.tbl_stride; i += G) L[i] = 0;
-                        ep = 1;
-                    }
-                    tag = ep << KX_TAG_SHIFT;
+                    guard = 0; status = lvl_ok ? 0u : 3u;      // 3: no double-fast row for this size at this level
+                    tag = kx_team_tag<G>(k, cl.ep, L, a.tbl_stride);
                     anchor = 0; ilimit = n - 8;
                     ip = 1; off1 = 1; off2 = 0;     // rep {1,4,8}: 4 exceeds the 1 byte of history at ip=1
                     step = 1; nextStep = ip + 256; carry = false; compl_due = false; have_pw = false;
@@ -466,16 +448,8 @@ KX_DEV void zstd_match_body(const KMatchArgs& a, DONE const& done = DONE())
                 if (bw) { m_start -= (int)back; m_mpos -= (int)back; lenA += back; off2 = off1; off1 = m_off; offBase = m_off + 3; }
                 else if (m_type == KMT_REP0) { u32 const t = off2; off2 = off1; off1 = t; }
                 int const ll = m_start - anchor;
-                if (!(a.flags & KXM_NO_LITS)) for (int c = 8 * k; c < ll; c += 8 * G) kx_st64(lits + nlit + c, kx_ld64_clamped(src, anchor + c, n));
-                {
-                    u64 const q = (u64)offBase | ((u64)(u16)ll << 32) | ((u64)(u16)(lenA - 3) << 48);   // KSeq
-                    u32 const slot = nseq & (2u * G - 1u);
-                    if ((u32)k == (slot >> 1)) { if (slot & 1u) sq1 = q; else sq0 = q; }
-                    if (slot == 2u * G - 1u) kx_st128(seqs + (nseq - slot) + 2u * (u32)k, sq0, sq1);
-                }
-                if (ll > 0xFFFF) { longType = 1; longPos = nseq; }
-                if (lenA - 3 > 0xFFFF) { longType = 2; longPos = nseq; }
-                nseq++; nlit += (u32)ll;
+                if (!(a.flags & KXM_NO_LITS)) for (int c = 8 * k; c < ll; c += 8 * G) kx_st64(lits + sink.nlit + c, kx_ld64_clamped(src, anchor + c, n));
+                sink.push<G>(k, offBase, ll, lenA - 3);
                 ip = m_start + (int)lenA; anchor = ip;
                 // the complementary inserts of this match wait for the bytes at the new position: the repcode-check block asks for them
                 compl_due = m_type != KMT_REP0 && ip <= ilimit;
@@ -489,16 +463,9 @@ KX_DEV void zstd_match_body(const KMatchArgs& a, DONE const& done = DONE())
         if (kx_any(state == KST_CLEANUP)) {
             bool const fin = state == KST_CLEANUP;
             if (fin) {
-                {
-                    u32 const cnt = nseq & (2u * G - 1u);       // sequences still in registers
-                    u64* const sp = (u64*)(seqs + (nseq - cnt));
-                    if (2u * (u32)k < cnt) sp[2 * k] = sq0;
-                    if (2u * (u32)k + 1u < cnt) sp[2 * k + 1] = sq1;
-                }
+                sink.flush<G>(k);
                 if (k == 0) {
-                    KSliceMeta mm;
-                    mm.nbSeq = nseq; mm.litSize = nlit; mm.lastLL = (u32)(n - anchor);
-                    mm.longType = longType; mm.longPos = longPos; mm.status = status; mm.pad[0] = 0; mm.pad[1] = 0;
+                    KSliceMeta mm = sink.meta((u32)(n - anchor), status);
                     if (!BLK && (a.flags & KXM_TIMESTAMPS)) { u64 const t = kx_realtime(); mm.pad[0] = (u32)t; mm.pad[1] = (u32)(t >> 32); }   // diagnostics: when the slice was done (100 MHz ticks)
                     if (BLK) {
                         // repcodes this block leaves behind (taken over by the frame only if the block is emitted compressed)
@@ -516,11 +483,11 @@ KX_DEV void zstd_match_body(const KMatchArgs& a, DONE const& done = DONE())
                 // comes back afterwards, so that nothing of it lives across the call (left to the register allocator, the spills
                 // land inside the search loop).
                 u32 sv[64];
-#define KX_MS32(X) X(state) X(n) X(ilimit) X(slice) X(ip) X(anchor) X(off1) X(off2) X(step) X(nextStep) X(nseq) X(nlit) X(tag) X(hbL) X(hbS) X(mls) \
-                   X(longType) X(longPos) X(guard) X(status) X(m_type) X(m_pos) X(m_start) X(m_mpos) X(m_len0) X(m_off) X(m_idxl1) X(carry_idxl) X(kmax) \
+#define KX_MS32(X) X(state) X(n) X(ilimit) X(slice) X(ip) X(anchor) X(off1) X(off2) X(step) X(nextStep) X(sink.nseq) X(sink.nlit) X(tag) X(hbL) X(hbS) X(mls) \
+                   X(sink.longType) X(sink.longPos) X(guard) X(status) X(m_type) X(m_pos) X(m_start) X(m_mpos) X(m_len0) X(m_off) X(m_idxl1) X(carry_idxl) X(kmax) \
                    X(c_pos) X(lowIdx) X(bstart) X(saved1) X(saved2)
-#define KX_MS64(X) X(m_w1) X(sq0) X(sq1) X(wa) X(pw)
-#define KX_MSP(X) X(src) X(seqs) X(lits) X(L) X(S)
+#define KX_MS64(X) X(m_w1) X(sink.sq0) X(sink.sq1) X(wa) X(pw)
+#define KX_MSP(X) X(src) X(sink.seqs) X(lits) X(L) X(S)
                 {
                     int q = 0;
 #define KX_SAVE32(x) sv[q++] = (u32)(x);

@@ -67,24 +67,19 @@ KX_DEV void zstd_match2_body(const KMatchArgs& a)
     constexpr int RS = R + 16;                       // the ring and a copy of its first 16 bytes behind it (reads never wrap)
     constexpr u32 lowIdx = 2u;
     KX_SHARED KxQuad ring_store[NT * RS / 16];
-    int const lane = kx_lane();
-    int const k = lane & (G - 1);
-    int const tbase = lane - k;
+    auto const [lane, k, tbase, tmask, team] = kx_team<G>(0);
     u8* const ring = (u8*)ring_store + (lane / G) * RS;
-    u32 const team = kx_block() * NT + (u32)(lane / G);
     u32* const L = kx_team_tables(a, team);
     u32* const S = L + KX_TBL_LONG;
-    u64 const tmask = (1ull << G) - 1ull;
     bool const nt_st = (a.flags & KXM_NT_STORES) != 0;
 
     // ---- team state (uniform across the team's lanes) -------------------
     int state = K2_IDLE;
     const u8* src = a.src; int n = 0; int ilimit = 0; u32 slice = 0;
     int ip = 0, anchor = 0; u32 off1 = 0, off2 = 0; int step = 1; int nextStep = 0;
-    u32 nseq = 0, nlit = 0; u32 tag = 0; u32 hbL = 16, hbS = 15, mls = 5;
-    u32 longType = 0, longPos = 0; u32 guard = 0; u32 status = 0;
-    KSeq* seqs = a.seqs;
-    u64 sq0 = 0, sq1 = 0;
+    u32 tag = 0; u32 hbL = 16, hbS = 15, mls = 5;
+    u32 guard = 0; u32 status = 0;
+    KSeqSink sink = { a.seqs };
     int wlo = 0, whi = 0;                            // the window holds src[max(wlo, whi - R), whi)
     bool chk0 = false;                               // a match just ended at ip: the immediate repcode test is due
     bool compl_due = false; u64 wa = 0; int c_pos = 0;   // ... and its complementary inserts (wa = the bytes at c_pos + 2)
@@ -100,31 +95,19 @@ KX_DEV void zstd_match2_body(const KMatchArgs& a)
     for (;;) {
         // ================= fetch the next slice (rare: its own round trip) =======================
         if (kx_any(state == K2_IDLE)) {
-            u32 s = 0, ep = 0;
-            if (state == K2_IDLE && k == 0) {
-                s = kx_atomic_add(a.counter, 1u);
-                if (s < a.n_slices) {
-                    ep = a.team_epoch[team] + 1;
-                    if (ep > KX_EPOCH_MAX) ep = 0;          // 0 = "clear the tables, restart at 1"
-                    a.team_epoch[team] = ep ? ep : 1u;
-                }
-            }
-            s = kx_shfl(s, tbase); ep = kx_shfl(ep, tbase);
+            KClaim const cl = kx_team_claim<true>(state == K2_IDLE && k == 0, tbase, a.counter, a.n_slices, a.team_epoch + team);
+            u32 const s = cl.s;
             if (state == K2_IDLE) {
                 if (s >= a.n_slices) state = K2_DONE;
                 else {
                     slice = s;
                     src = a.src + a.in_off[s];
                     n = (int)a.in_len[s];
-                    seqs = a.seqs + (size_t)s * a.seq_cap;
+                    sink.reset(a.seqs + (size_t)s * a.seq_cap);
                     KParams const P = kx_params_l3((u32)n);
                     hbL = P.hashLog; hbS = P.chainLog; mls = P.minMatch;
-                    nseq = 0; nlit = 0; longType = 0; longPos = 0; guard = 0; status = 0;
-                    if (ep == 0) {
-                        for (u32 i = (u32)k; i < KX_TBL_ENTRIES; i += G) L[i] = 0;
-                        ep = 1;
-                    }
-                    tag = ep << KX_TAG_SHIFT;
+                    guard = 0; status = 0;
+                    tag = kx_team_tag<G>(k, cl.ep, L, KX_TBL_ENTRIES);
                     anchor = 0; ilimit = n - 8;
                     ip = 1; off1 = 1; off2 = 0;     // rep {1,4,8}: 4 exceeds the 1 byte of history at ip=1
                     step = 1; nextStep = ip + 256;
@@ -479,15 +462,7 @@ KX_DEV void zstd_match2_body(const KMatchArgs& a)
                 if (bw) { m_start -= (int)back; m_mpos -= (int)back; lenA += back; off2 = off1; off1 = m_off; offBase = m_off + 3; }
                 else if (m_type == KMT_REP0) { u32 const t = off2; off2 = off1; off1 = t; }
                 int const ll = m_start - anchor;
-                {
-                    u64 const q = (u64)offBase | ((u64)(u16)ll << 32) | ((u64)(u16)(lenA - 3) << 48);   // KSeq
-                    u32 const slot = nseq & (2u * G - 1u);
-                    if ((u32)k == (slot >> 1)) { if (slot & 1u) sq1 = q; else sq0 = q; }
-                    if (slot == 2u * G - 1u) kx_st128(seqs + (nseq - slot) + 2u * (u32)k, sq0, sq1);
-                }
-                if (ll > 0xFFFF) { longType = 1; longPos = nseq; }
-                if (lenA - 3 > 0xFFFF) { longType = 2; longPos = nseq; }
-                nseq++; nlit += (u32)ll;
+                sink.push<G>(k, offBase, ll, lenA - 3);
                 ip = m_start + (int)lenA; anchor = ip;
                 compl_due = m_type != KMT_REP0 && ip <= ilimit;
                 chk0 = true; step = 1; nextStep = ip + 256; have_w = false;
@@ -498,16 +473,9 @@ KX_DEV void zstd_match2_body(const KMatchArgs& a)
         // ================= finish the slice ===========================
         if (kx_any(state == K2_CLEANUP)) {
             if (state == K2_CLEANUP) {
-                {
-                    u32 const cnt = nseq & (2u * G - 1u);       // sequences still in registers
-                    u64* const sp = (u64*)(seqs + (nseq - cnt));
-                    if (2u * (u32)k < cnt) sp[2 * k] = sq0;
-                    if (2u * (u32)k + 1u < cnt) sp[2 * k + 1] = sq1;
-                }
+                sink.flush<G>(k);
                 if (k == 0) {
-                    KSliceMeta mm;
-                    mm.nbSeq = nseq; mm.litSize = nlit; mm.lastLL = (u32)(n - anchor);
-                    mm.longType = longType; mm.longPos = longPos; mm.status = status; mm.pad[0] = 0; mm.pad[1] = 0;
+                    KSliceMeta mm = sink.meta((u32)(n - anchor), status);
                     a.meta[slice] = mm;
                 }
                 state = K2_IDLE;

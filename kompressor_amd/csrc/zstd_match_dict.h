@@ -3,7 +3,7 @@
 // ZSTD_CCtx_loadDictionary, then the one-shot ZSTD_compressStream2 at :112).
 //
 // libzstd 1.5.7 turns the dictionary into a CDict (tables sized for the dictionary, built once: here by the host,
-// kmp_batch.hip) and then parses every input with one of two double-fast variants, both a plain position-by-position
+// zstd_cdict_host.h) and then parses every input with one of two double-fast variants, both a plain position-by-position
 // loop (no pipelined look-ahead as in the dictionary-less parser):
 //   * input <= 16 KiB: the CDict stays attached; its (tagged) tables are consulted when the working tables miss
 //     ("dictMatchState");
@@ -97,46 +97,33 @@ enum { KDS_IDLE = 0, KDS_SEARCH = 1, KDS_REPLOOP = 2, KDS_MATCH = 3, KDS_CLEANUP
 template <int G>
 KX_DEV void zstd_match_dict_body(const KDictArgs& d)
 {
-    constexpr int NT = 64 / G;
     const KMatchArgs& a = d.m;
-    int const lane = kx_lane();
-    int const k = lane & (G - 1);
-    int const tbase = lane - k;
-    u32 const team = kx_block() * NT + (u32)(lane / G);
+    auto const [lane, k, tbase, tmask, team] = kx_team<G>(0);
     u32* const L = kx_team_tables(a, team);
     u32* const S = L + KX_TBL_LONG;
-    u64 const tmask = (G == 64) ? ~0ull : ((1ull << G) - 1ull);
     int const D = (int)d.dict_size;
     u32 const P = 2u + (u32)D;                            // index of the input's first byte
 
     int state = KDS_IDLE;
     KV v; v.dict = d.dict; v.D = D; v.src = a.src; v.n = 0;
     int n = 0, ilimit = 0; u32 slice = 0; bool attach = false;
-    int ip = 0, anchor = 0; u32 off1 = 1, off2 = 4; u32 nseq = 0, nlit = 0, tag = 0; u32 hbL = 16, hbS = 15, mls = 5;
-    u32 longType = 0, longPos = 0, guard = 0, status = 0;
-    KSeq* seqs = a.seqs; u64 sq0 = 0, sq1 = 0;
+    int ip = 0, anchor = 0; u32 off1 = 1, off2 = 4; u32 tag = 0; u32 hbL = 16, hbS = 15, mls = 5;
+    u32 guard = 0, status = 0;
+    KSeqSink sink = { a.seqs };
     // pending match (virtual positions)
     int m_start = 0, m_mv = 0, m_low = 0, m_curr = 0; u32 m_len0 = 0, m_off = 0; bool m_back = false;
 
     for (;;) {
         // ================= next slice ==================================
         if (kx_any(state == KDS_IDLE)) {
-            u32 s = 0, ep = 0;
-            if (state == KDS_IDLE && k == 0) {
-                s = kx_atomic_add(a.counter, 1u);
-                if (s < a.n_slices) {
-                    ep = a.team_epoch[team] + 1;
-                    if (ep > KX_EPOCH_MAX) ep = 0;
-                    a.team_epoch[team] = ep ? ep : 1u;
-                }
-            }
-            s = kx_shfl(s, tbase); ep = kx_shfl(ep, tbase);
+            KClaim const cl = kx_team_claim<true>(state == KDS_IDLE && k == 0, tbase, a.counter, a.n_slices, a.team_epoch + team);
+            u32 const s = cl.s;
             if (state == KDS_IDLE) {
                 if (s >= a.n_slices) state = KDS_DONE;
                 else {
                     slice = s;
                     v.src = a.src + a.in_off[s]; n = (int)a.in_len[s]; v.n = n;
-                    seqs = a.seqs + (size_t)s * a.seq_cap;
+                    sink.reset(a.seqs + (size_t)s * a.seq_cap);
                     attach = n <= 16 * 1024;                     // attachDictSizeCutoffs[ZSTD_dfast]
                     hbL = d.dHashLog; hbS = d.dChainLog; mls = d.dMinMatch;
                     if (attach) {
@@ -146,12 +133,8 @@ KX_DEV void zstd_match_dict_body(const KDictArgs& d)
                         if (hbL > W + 1) hbL = W + 1;
                         if (hbS > W) hbS = W;
                     }
-                    nseq = 0; nlit = 0; longType = 0; longPos = 0; guard = 0; status = 0;
-                    if (ep == 0) {
-                        for (u32 i = (u32)k; i < KX_TBL_ENTRIES; i += G) L[i] = 0;
-                        ep = 1;
-                    }
-                    tag = ep << KX_TAG_SHIFT;
+                    guard = 0; status = 0;
+                    tag = kx_team_tag<G>(k, cl.ep, L, KX_TBL_ENTRIES);
                     anchor = 0; ip = 0; ilimit = n - 8; off1 = d.rep0; off2 = d.rep1;
                     state = (n < 8 || ip >= ilimit) ? KDS_CLEANUP : KDS_SEARCH;
                 }
@@ -294,15 +277,7 @@ KX_DEV void zstd_match_dict_body(const KDictArgs& d)
                 u32 offBase = 1;
                 if (m_back) { m_start -= (int)back; lenA += back; off2 = off1; off1 = m_off; offBase = m_off + 3; }
                 int const ll = m_start - anchor;
-                {
-                    u64 const q = (u64)offBase | ((u64)(u16)ll << 32) | ((u64)(u16)(lenA - 3) << 48);   // KSeq
-                    u32 const slot = nseq & (2u * G - 1u);
-                    if ((u32)k == (slot >> 1)) { if (slot & 1u) sq1 = q; else sq0 = q; }
-                    if (slot == 2u * G - 1u) kx_st128(seqs + (nseq - slot) + 2u * (u32)k, sq0, sq1);
-                }
-                if (ll > 0xFFFF) { longType = 1; longPos = nseq; }
-                if (lenA - 3 > 0xFFFF) { longType = 2; longPos = nseq; }
-                nseq++; nlit += (u32)ll;
+                sink.push<G>(k, offBase, ll, lenA - 3);
                 ip = m_start + (int)lenA; anchor = ip;
                 if (m_curr >= 0 && ip <= ilimit && k == 0) {
                     // complementary insertion: curr+2 into both tables, then ip-2 (long) and ip-1 (short)
@@ -321,16 +296,9 @@ KX_DEV void zstd_match_dict_body(const KDictArgs& d)
         // ================= finish the slice ==================================
         if (kx_any(state == KDS_CLEANUP)) {
             if (state == KDS_CLEANUP) {
-                {
-                    u32 const cnt = nseq & (2u * G - 1u);
-                    u64* const sp = (u64*)(seqs + (nseq - cnt));
-                    if (2u * (u32)k < cnt) sp[2 * k] = sq0;
-                    if (2u * (u32)k + 1u < cnt) sp[2 * k + 1] = sq1;
-                }
+                sink.flush<G>(k);
                 if (k == 0) {
-                    KSliceMeta mm;
-                    mm.nbSeq = nseq; mm.litSize = nlit; mm.lastLL = (u32)(n - anchor);
-                    mm.longType = longType; mm.longPos = longPos; mm.status = status; mm.pad[0] = 0; mm.pad[1] = 0;
+                    KSliceMeta mm = sink.meta((u32)(n - anchor), status);
                     a.meta[slice] = mm;
                 }
                 state = KDS_IDLE;

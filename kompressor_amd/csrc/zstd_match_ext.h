@@ -21,28 +21,22 @@ enum { KXS_IDLE = 0, KXS_SEARCH = 1, KXS_REPLOOP = 2, KXS_MATCH = 3, KXS_CLEANUP
 template <int G>
 KX_DEV void zstd_match_ext_body(const KMatchArgs& a)
 {
-    int const lane = kx_lane();
-    int const k = lane & (G - 1);
-    int const tbase = lane - k;
-    u64 const tmask = (G == 64) ? ~0ull : ((1ull << G) - 1ull);
+    auto const [lane, k, tbase, tmask, team] = kx_team<G>(0);
     bool const wide = (a.flags & KXM_WIDE) != 0;
     u32 const IDXM = wide ? 0xFFFFFFFFu : KX_BLK_IDX_MASK;
     constexpr u32 CHKS = KX_BLK_IDX_BITS;
 
     int state = KXS_IDLE;
-    const u8* src = a.src; u32* L = a.big_tables; u32* S = a.big_tables; KSeq* seqs = a.seqs; u8* lits = a.lits;
+    const u8* src = a.src; u32* L = a.big_tables; u32* S = a.big_tables; KSeqSink sink = { a.seqs }; u8* lits = a.lits;
     int n = 0, ilimit = 0, ip = 0, anchor = 0; u32 slice = 0; u32 off1 = 1, off2 = 4;
-    u32 nseq = 0, nlit = 0, longType = 0, longPos = 0, guard = 0, status = 0; u32 hbL = 17, hbS = 16, mls = 5;
+    u32 guard = 0, status = 0; u32 hbL = 17, hbS = 16, mls = 5;
     u32 dsi = 2, psi = 2;                       // dictStartIndex, prefixStartIndex of the block
-    u64 sq0 = 0, sq1 = 0;
     int m_start = 0, m_mpos = 0, m_low = 0, m_curr = 0; u32 m_len0 = 0, m_off = 0; bool m_back = false;
 
     for (;;) {
         // ================= next slice whose block is an extDict block ==================
         if (kx_any(state == KXS_IDLE)) {
-            u32 s = 0;
-            if (state == KXS_IDLE && k == 0) s = kx_atomic_add(a.counter, 1u);
-            s = kx_shfl(s, tbase);
+            u32 const s = kx_team_claim<false>(state == KXS_IDLE && k == 0, tbase, a.counter, a.n_slices, nullptr).s;
             if (state == KXS_IDLE) {
                 if (s >= a.n_slices) state = KXS_DONE;
                 else {
@@ -54,11 +48,11 @@ KX_DEV void zstd_match_ext_body(const KMatchArgs& a)
                     if (fs.blockSize != 0 && bw.ext) {
                         slice = s;
                         src = a.src + a.in_off[s];
-                        seqs = a.seqs + (size_t)s * a.seq_cap; lits = a.lits + (size_t)s * a.lit_cap;
+                        sink.reset(a.seqs + (size_t)s * a.seq_cap); lits = a.lits + (size_t)s * a.lit_cap;
                         L = a.big_tables + (size_t)s * a.big_stride; S = L + a.big_long;
                         hbL = P.hashLog; hbS = P.chainLog; mls = P.minMatch;
                         dsi = bw.dictStartIndex; psi = bw.prefixStartIndex;
-                        nseq = 0; nlit = 0; longType = 0; longPos = 0; guard = 0; status = 0;
+                        guard = 0; status = 0;
                         ip = (int)fs.ipos; anchor = ip; n = ip + (int)fs.blockSize; ilimit = n - 8;
                         off1 = fs.rep[0]; off2 = fs.rep[1];
                         state = (fs.blockSize < 8 || ip >= ilimit) ? KXS_CLEANUP : KXS_SEARCH;
@@ -157,16 +151,8 @@ KX_DEV void zstd_match_ext_body(const KMatchArgs& a)
                 if (m_back) { m_start -= (int)back; lenA += back; off2 = off1; off1 = m_off; offBase = m_off + 3; }
                 int const ll = m_start - anchor;
                 // the literals in front of the match (the block-chain kernel codes them from this buffer)
-                if (!(a.flags & KXM_NO_LITS)) for (int c = 8 * k; c < ll; c += 8 * G) kx_st64(lits + nlit + c, kx_ld64_clamped(src, anchor + c, n));
-                {
-                    u64 const q = (u64)offBase | ((u64)(u16)ll << 32) | ((u64)(u16)(lenA - 3) << 48);   // KSeq
-                    u32 const slot = nseq & (2u * G - 1u);
-                    if ((u32)k == (slot >> 1)) { if (slot & 1u) sq1 = q; else sq0 = q; }
-                    if (slot == 2u * G - 1u) kx_st128(seqs + (nseq - slot) + 2u * (u32)k, sq0, sq1);
-                }
-                if (ll > 0xFFFF) { longType = 1; longPos = nseq; }
-                if (lenA - 3 > 0xFFFF) { longType = 2; longPos = nseq; }
-                nseq++; nlit += (u32)ll;
+                if (!(a.flags & KXM_NO_LITS)) for (int c = 8 * k; c < ll; c += 8 * G) kx_st64(lits + sink.nlit + c, kx_ld64_clamped(src, anchor + c, n));
+                sink.push<G>(k, offBase, ll, lenA - 3);
                 ip = m_start + (int)lenA; anchor = ip;
                 if (m_curr >= 0 && ip <= ilimit && k == 0) {
                     // complementary insertion: curr+2 into both tables, then ip-2 (long) and ip-1 (short)
@@ -185,16 +171,9 @@ KX_DEV void zstd_match_ext_body(const KMatchArgs& a)
         // ================= finish the block ==================================
         if (kx_any(state == KXS_CLEANUP)) {
             if (state == KXS_CLEANUP) {
-                {
-                    u32 const cnt = nseq & (2u * G - 1u);
-                    u64* const sp = (u64*)(seqs + (nseq - cnt));
-                    if (2u * (u32)k < cnt) sp[2 * k] = sq0;
-                    if (2u * (u32)k + 1u < cnt) sp[2 * k + 1] = sq1;
-                }
+                sink.flush<G>(k);
                 if (k == 0) {
-                    KSliceMeta mm;
-                    mm.nbSeq = nseq; mm.litSize = nlit; mm.lastLL = (u32)(n - anchor);
-                    mm.longType = longType; mm.longPos = longPos; mm.status = status;
+                    KSliceMeta mm = sink.meta((u32)(n - anchor), status);
                     mm.pad[0] = off1; mm.pad[1] = off2;                 // the extDict variant sets no repcode aside
                     a.meta[slice] = mm;
                 }

@@ -52,36 +52,23 @@ KX_DEV void zstd_match_fast_body(const KFastArgs& f)
     u32 const CHKM = BLK ? (wide ? 0u : KX_BLK_CHK_MASK) : KX_CHK_MASK;      // check bits (first 4 bytes of the position, what a candidate is compared on)
     u32 lowIdx = 2u;                                        // lowest valid index (position + 2): 2 unless the window has slid (block mode, long slices)
 #define KFS_CK(bytes4_) (wide ? 0u : kx_chk_short((u64)(bytes4_)) << (BLK ? KX_BLK_IDX_BITS : KX_CHK_SHIFT))
-    constexpr int NT = 64 / G;
     const KMatchArgs& a = f.m;
-    int const lane = kx_lane();
-    int const k = lane & (G - 1);
-    int const tbase = lane - k;
-    u32 const team = kx_block() * NT + (u32)(lane / G);
+    auto const [lane, k, tbase, tmask, team] = kx_team<G>(0);
     u32* H = BLK ? a.big_tables : kx_team_tables(a, team);
     int bstart = 0; u32 saved1 = 0, saved2 = 0;
-    u64 const tmask = (G == 64) ? ~0ull : ((1ull << G) - 1ull);
 
     int state = KFS_IDLE;
     const u8* src = a.src; int n = 0, ilimit = 0; u32 slice = 0;
-    int ip0 = 0, anchor = 0; u32 rep1 = 1, rep2 = 0; u32 nseq = 0, nlit = 0, tag = 0, hlog = 13, mls = 6;
+    int ip0 = 0, anchor = 0; u32 rep1 = 1, rep2 = 0; u32 tag = 0, hlog = 13, mls = 6;
     int step = 2, gap = 2, nextStep = 0; u32 hash0 = 0, hash1 = 0, matchIdx = 0; int current0 = 0;     // gap = distance from the pair to the next one
-    u32 longType = 0, longPos = 0, guard = 0, status = 0;
-    KSeq* seqs = a.seqs; u64 sq0 = 0, sq1 = 0;
+    u32 guard = 0, status = 0;
+    KSeqSink sink = { a.seqs };
     int m_start = 0, m_mpos = 0; u32 m_len0 = 0, m_off = 0; bool m_back = false, m_fill = false;
 
     for (;;) {
         if (kx_any(state == KFS_IDLE)) {
-            u32 s = 0, ep = 0;
-            if (state == KFS_IDLE && k == 0) {
-                s = kx_atomic_add(a.counter, 1u);
-                if (!BLK && s < a.n_slices) {
-                    ep = a.team_epoch[team] + 1;
-                    if (ep > KX_EPOCH_MAX) ep = 0;
-                    a.team_epoch[team] = ep ? ep : 1u;
-                }
-            }
-            s = kx_shfl(s, tbase); ep = kx_shfl(ep, tbase);
+            KClaim const cl = kx_team_claim<!BLK>(state == KFS_IDLE && k == 0, tbase, a.counter, a.n_slices, a.team_epoch + team);
+            u32 const s = cl.s;
             if (state == KFS_IDLE) {
                 if (s >= a.n_slices) state = KFS_DONE;
                 else if (BLK) {
@@ -91,11 +78,11 @@ KX_DEV void zstd_match_fast_body(const KFastArgs& f)
                     if (fs.blockSize != 0 && !bw.ext && kx_in_class((a.flags >> KXM_CLASS_SHIFT) & KXM_CLASS_MASK, a.in_len[s])) {
                         slice = s;
                         src = a.src + a.in_off[s];
-                        seqs = a.seqs + (size_t)s * a.seq_cap;
+                        sink.reset(a.seqs + (size_t)s * a.seq_cap);
                         H = a.big_tables + (size_t)s * KX_BIG_TBL_ENTRIES;
                         kx_params_fast(f.level, a.in_len[s], hlog, mls);
                         if (a.flags & KXM_STREAM_PARAMS) { hlog = f.level == 2 ? 16 : f.level == 0 ? 13 : 14; mls = f.level == 1 ? 7 : 6; }      // size unknown: level 1 window 19, hash 14, minMatch 7; level 2 window 20, hash 16, minMatch 6; negative levels window 19, hash 13, minMatch 6
-                        nseq = 0; nlit = 0; longType = 0; longPos = 0; guard = 0; status = 0; tag = 0;
+                        guard = 0; status = 0; tag = 0;
                         bstart = (int)fs.ipos; n = bstart + (int)fs.blockSize;   // n = end of the block
                         anchor = bstart; ilimit = n - 8;
                         // candidates: valid from ZSTD_getLowestPrefixIndex at the block's END on; the repcodes are checked against the
@@ -111,14 +98,10 @@ KX_DEV void zstd_match_fast_body(const KFastArgs& f)
                 } else {
                     slice = s;
                     src = a.src + a.in_off[s]; n = (int)a.in_len[s];
-                    seqs = a.seqs + (size_t)s * a.seq_cap;
+                    sink.reset(a.seqs + (size_t)s * a.seq_cap);
                     kx_params_fast(f.level, (u32)n, hlog, mls);
-                    nseq = 0; nlit = 0; longType = 0; longPos = 0; guard = 0; status = 0;
-                    if (ep == 0) {
-                        for (u32 i = (u32)k; i < KX_TBL_ENTRIES; i += G) H[i] = 0;
-                        ep = 1;
-                    }
-                    tag = ep << KX_TAG_SHIFT;
+                    guard = 0; status = 0;
+                    tag = kx_team_tag<G>(k, cl.ep, H, KX_TBL_ENTRIES);
                     anchor = 0; ilimit = n - 8;
                     ip0 = 1; rep1 = 1; rep2 = 0;             // rep {1,4,8}: 4 exceeds the 1 byte of history at ip0 = 1
                     state = (n < 8) ? KFS_CLEANUP : KFS_START;
@@ -278,15 +261,7 @@ KX_DEV void zstd_match_fast_body(const KFastArgs& f)
                 u32 offBase = 1;
                 if (m_back) { m_start -= (int)back; lenA += back; rep2 = rep1; rep1 = m_off; offBase = m_off + 3; }
                 int const ll = m_start - anchor;
-                {
-                    u64 const q = (u64)offBase | ((u64)(u16)ll << 32) | ((u64)(u16)(lenA - 3) << 48);   // KSeq
-                    u32 const slot = nseq & (2u * G - 1u);
-                    if ((u32)k == (slot >> 1)) { if (slot & 1u) sq1 = q; else sq0 = q; }
-                    if (slot == 2u * G - 1u) kx_st128(seqs + (nseq - slot) + 2u * (u32)k, sq0, sq1);
-                }
-                if (ll > 0xFFFF) { longType = 1; longPos = nseq; }
-                if (lenA - 3 > 0xFFFF) { longType = 2; longPos = nseq; }
-                nseq++; nlit += (u32)ll;
+                sink.push<G>(k, offBase, ll, lenA - 3);
                 ip0 = m_start + (int)lenA; anchor = ip0;
                 if (m_fill && ip0 <= ilimit && k == 0) {
                     // fill: current0 + 2 and ip0 - 2
@@ -302,16 +277,9 @@ KX_DEV void zstd_match_fast_body(const KFastArgs& f)
         // ================= finish the slice ==================================
         if (kx_any(state == KFS_CLEANUP)) {
             if (state == KFS_CLEANUP) {
-                {
-                    u32 const cnt = nseq & (2u * G - 1u);
-                    u64* const sp = (u64*)(seqs + (nseq - cnt));
-                    if (2u * (u32)k < cnt) sp[2 * k] = sq0;
-                    if (2u * (u32)k + 1u < cnt) sp[2 * k + 1] = sq1;
-                }
+                sink.flush<G>(k);
                 if (k == 0) {
-                    KSliceMeta mm;
-                    mm.nbSeq = nseq; mm.litSize = nlit; mm.lastLL = (u32)(n - anchor);
-                    mm.longType = longType; mm.longPos = longPos; mm.status = status; mm.pad[0] = 0; mm.pad[1] = 0;
+                    KSliceMeta mm = sink.meta((u32)(n - anchor), status);
                     if (BLK) {
                         u32 const s2 = (saved1 != 0 && rep1 != 0) ? saved1 : saved2;
                         mm.pad[0] = rep1 ? rep1 : saved1; mm.pad[1] = rep2 ? rep2 : s2;
@@ -346,26 +314,20 @@ KX_DEV void zstd_match_fast_ext_body(const KFastArgs& f)
     bool const wide = (a.flags & KXM_WIDE) != 0;
     u32 const IDXM = wide ? 0xFFFFFFFFu : KX_BLK_IDX_MASK;
 #define KFX_E(bytes4_, idx_) ((u32)(idx_) | (wide ? 0u : kx_chk_short((u64)(bytes4_)) << KX_BLK_IDX_BITS))
-    int const lane = kx_lane();
-    int const k = lane & (G - 1);
-    int const tbase = lane - k;
-    u64 const tmask = (G == 64) ? ~0ull : ((1ull << G) - 1ull);
+    auto const [lane, k, tbase, tmask, team] = kx_team<G>(0);
 
     int state = KFX_IDLE;
-    const u8* src = a.src; u32* H = a.big_tables; KSeq* seqs = a.seqs;
+    const u8* src = a.src; u32* H = a.big_tables; KSeqSink sink = { a.seqs };
     int n = 0, ilimit = 0, ip0 = 0, anchor = 0; u32 slice = 0; u32 off1 = 1, off2 = 4, saved1 = 0, saved2 = 0;
-    u32 nseq = 0, nlit = 0, longType = 0, longPos = 0, guard = 0, status = 0, hlog = 14, mls = 7;
+    u32 guard = 0, status = 0, hlog = 14, mls = 7;
     u32 dsi = 2, psi = 2;                       // dictStartIndex, prefixStartIndex of the block
     int step = 2, gap = 2, nextStep = 0; u32 hash0 = 0, hash1 = 0, idx = 0;         // gap = distance from the pair to the next one (the step in force when it was laid out)
-    u64 sq0 = 0, sq1 = 0;
     int m_start = 0, m_mpos = 0, m_low = 0, m_cur0 = 0, m_ip1 = 0; u32 m_len0 = 0, m_off = 0, m_hash1 = 0; bool m_back = false, m_fill = false;
 
     for (;;) {
         // ================= next slice whose block is an extDict block ==================
         if (kx_any(state == KFX_IDLE)) {
-            u32 s = 0;
-            if (state == KFX_IDLE && k == 0) s = kx_atomic_add(a.counter, 1u);
-            s = kx_shfl(s, tbase);
+            u32 const s = kx_team_claim<false>(state == KFX_IDLE && k == 0, tbase, a.counter, a.n_slices, nullptr).s;
             if (state == KFX_IDLE) {
                 if (s >= a.n_slices) state = KFX_DONE;
                 else {
@@ -374,12 +336,12 @@ KX_DEV void zstd_match_fast_ext_body(const KFastArgs& f)
                     if (fs.blockSize != 0 && bw.ext && kx_in_class((a.flags >> KXM_CLASS_SHIFT) & KXM_CLASS_MASK, a.in_len[s])) {
                         slice = s;
                         src = a.src + a.in_off[s];
-                        seqs = a.seqs + (size_t)s * a.seq_cap;
+                        sink.reset(a.seqs + (size_t)s * a.seq_cap);
                         H = a.big_tables + (size_t)s * KX_BIG_TBL_ENTRIES;
                         kx_params_fast(f.level, a.in_len[s], hlog, mls);
                         if (a.flags & KXM_STREAM_PARAMS) { hlog = f.level == 2 ? 16 : f.level == 0 ? 13 : 14; mls = f.level == 1 ? 7 : 6; }
                         dsi = bw.dictStartIndex; psi = bw.prefixStartIndex;
-                        nseq = 0; nlit = 0; longType = 0; longPos = 0; guard = 0; status = 0;
+                        guard = 0; status = 0;
                         ip0 = (int)fs.ipos; anchor = ip0; n = ip0 + (int)fs.blockSize; ilimit = n - 8;
                         off1 = fs.rep[0]; off2 = fs.rep[1]; saved1 = 0; saved2 = 0;
                         u32 const maxRep = ((u32)ip0 + 2u) - dsi;
@@ -502,15 +464,7 @@ KX_DEV void zstd_match_fast_ext_body(const KFastArgs& f)
                 u32 offBase = 1;
                 if (m_back) { m_start -= (int)back; lenA += back; off2 = off1; off1 = m_off; offBase = m_off + 3; }
                 int const ll = m_start - anchor;
-                {
-                    u64 const q = (u64)offBase | ((u64)(u16)ll << 32) | ((u64)(u16)(lenA - 3) << 48);   // KSeq
-                    u32 const slot = nseq & (2u * G - 1u);
-                    if ((u32)k == (slot >> 1)) { if (slot & 1u) sq1 = q; else sq0 = q; }
-                    if (slot == 2u * G - 1u) kx_st128(seqs + (nseq - slot) + 2u * (u32)k, sq0, sq1);
-                }
-                if (ll > 0xFFFF) { longType = 1; longPos = nseq; }
-                if (lenA - 3 > 0xFFFF) { longType = 2; longPos = nseq; }
-                nseq++; nlit += (u32)ll;
+                sink.push<G>(k, offBase, ll, lenA - 3);
                 ip0 = m_start + (int)lenA; anchor = ip0;
                 if (m_fill && k == 0) {
                     // the pair's other position, if the match has not swallowed it; then the fill: current0 + 2 and ip0 - 2
@@ -529,16 +483,9 @@ KX_DEV void zstd_match_fast_ext_body(const KFastArgs& f)
         // ================= finish the block ==================================
         if (kx_any(state == KFX_CLEANUP)) {
             if (state == KFX_CLEANUP) {
-                {
-                    u32 const cnt = nseq & (2u * G - 1u);
-                    u64* const sp = (u64*)(seqs + (nseq - cnt));
-                    if (2u * (u32)k < cnt) sp[2 * k] = sq0;
-                    if (2u * (u32)k + 1u < cnt) sp[2 * k + 1] = sq1;
-                }
+                sink.flush<G>(k);
                 if (k == 0) {
-                    KSliceMeta mm;
-                    mm.nbSeq = nseq; mm.litSize = nlit; mm.lastLL = (u32)(n - anchor);
-                    mm.longType = longType; mm.longPos = longPos; mm.status = status;
+                    KSliceMeta mm = sink.meta((u32)(n - anchor), status);
                     u32 const s2 = (saved1 != 0 && off1 != 0) ? saved1 : saved2;
                     mm.pad[0] = off1 ? off1 : saved1; mm.pad[1] = off2 ? off2 : s2;
                     a.meta[slice] = mm;

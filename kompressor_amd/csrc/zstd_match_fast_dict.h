@@ -43,24 +43,19 @@ enum { KFD_IDLE = 0, KFD_DMS = 1, KFD_START = 2, KFD_PAIR = 3, KFD_REPLOOP = 4, 
 template <int G>
 KX_DEV void zstd_match_fast_dict_body(const KFastDictArgs& d)
 {
-    constexpr int NT = 64 / G;
     const KMatchArgs& a = d.m;
-    int const lane = kx_lane();
-    int const k = lane & (G - 1);
-    int const tbase = lane - k;
-    u32 const team = kx_block() * NT + (u32)(lane / G);
+    auto const [lane, k, tbase, tmask, team] = kx_team<G>(0);
     u32* const H = kx_team_tables(a, team);
-    u64 const tmask = (G == 64) ? ~0ull : ((1ull << G) - 1ull);
     int const D = (int)d.dict_size;
     u32 const P = 2u + (u32)D;                            // index of the input's first byte (prefixStartIndex; dictStartIndex is 2)
 
     int state = KFD_IDLE;
     KV v; v.dict = d.dict; v.D = D; v.src = a.src; v.n = 0;
     int n = 0, ilimit = 0; u32 slice = 0; bool attach = false;
-    int ip0 = 0, ip1 = 0, anchor = 0; u32 off1 = 1, off2 = 4; u32 nseq = 0, nlit = 0, tag = 0, hlog = 13, mls = 5;
+    int ip0 = 0, ip1 = 0, anchor = 0; u32 off1 = 1, off2 = 4; u32 tag = 0, hlog = 13, mls = 5;
     int step = 1, gap = 1, nextStep = 0; u32 hash0 = 0, hash1 = 0, idx = 0;        // (copied-table variant) gap = distance from the pair to the next one
-    u32 longType = 0, longPos = 0, guard = 0, status = 0;
-    KSeq* seqs = a.seqs; u64 sq0 = 0, sq1 = 0;
+    u32 guard = 0, status = 0;
+    KSeqSink sink = { a.seqs };
     // pending match (virtual positions); m_cur0: the searched position whose successor is inserted behind the match, -1: none;
     // m_ip1 / m_hash1: the pair's other position (copied-table variant), inserted when the match has not swallowed it
     int m_start = 0, m_mv = 0, m_low = 0, m_cur0 = 0, m_ip1 = -1; u32 m_len0 = 0, m_off = 0, m_hash1 = 0; bool m_back = false;
@@ -70,22 +65,14 @@ KX_DEV void zstd_match_fast_dict_body(const KFastDictArgs& d)
     for (;;) {
         // ================= next slice ==================================
         if (kx_any(state == KFD_IDLE)) {
-            u32 s = 0, ep = 0;
-            if (state == KFD_IDLE && k == 0) {
-                s = kx_atomic_add(a.counter, 1u);
-                if (s < a.n_slices) {
-                    ep = a.team_epoch[team] + 1;
-                    if (ep > KX_EPOCH_MAX) ep = 0;
-                    a.team_epoch[team] = ep ? ep : 1u;
-                }
-            }
-            s = kx_shfl(s, tbase); ep = kx_shfl(ep, tbase);
+            KClaim const cl = kx_team_claim<true>(state == KFD_IDLE && k == 0, tbase, a.counter, a.n_slices, a.team_epoch + team);
+            u32 const s = cl.s;
             if (state == KFD_IDLE) {
                 if (s >= a.n_slices) state = KFD_DONE;
                 else {
                     slice = s;
                     v.src = a.src + a.in_off[s]; n = (int)a.in_len[s]; v.n = n;
-                    seqs = a.seqs + (size_t)s * a.seq_cap;
+                    sink.reset(a.seqs + (size_t)s * a.seq_cap);
                     attach = n <= (int)KX_FAST_ATTACH_MAX;
                     hlog = d.dHashLog; mls = d.dMinMatch;
                     if (attach) {
@@ -94,12 +81,8 @@ KX_DEV void zstd_match_fast_dict_body(const KFastDictArgs& d)
                         u32 const W = d.dWindowLog < srcLog ? d.dWindowLog : srcLog;
                         if (hlog > W + 1) hlog = W + 1;
                     }
-                    nseq = 0; nlit = 0; longType = 0; longPos = 0; guard = 0; status = 0;
-                    if (ep == 0) {
-                        for (u32 i = (u32)k; i < KX_TBL_ENTRIES; i += G) H[i] = 0;
-                        ep = 1;
-                    }
-                    tag = ep << KX_TAG_SHIFT;
+                    guard = 0; status = 0;
+                    tag = kx_team_tag<G>(k, cl.ep, H, KX_TBL_ENTRIES);
                     anchor = 0; ip0 = 0; ilimit = n - 8; off1 = d.rep0; off2 = d.rep1;
                     if (attach) {
                         step = (int)d.step; ip1 = step; nextStep = 256;
@@ -273,15 +256,7 @@ KX_DEV void zstd_match_fast_dict_body(const KFastDictArgs& d)
                 u32 offBase = 1;
                 if (m_back) { m_start -= (int)back; lenA += back; off2 = off1; off1 = m_off; offBase = m_off + 3; }
                 int const ll = m_start - anchor;
-                {
-                    u64 const q = (u64)offBase | ((u64)(u16)ll << 32) | ((u64)(u16)(lenA - 3) << 48);   // KSeq
-                    u32 const slot = nseq & (2u * G - 1u);
-                    if ((u32)k == (slot >> 1)) { if (slot & 1u) sq1 = q; else sq0 = q; }
-                    if (slot == 2u * G - 1u) kx_st128(seqs + (nseq - slot) + 2u * (u32)k, sq0, sq1);
-                }
-                if (ll > 0xFFFF) { longType = 1; longPos = nseq; }
-                if (lenA - 3 > 0xFFFF) { longType = 2; longPos = nseq; }
-                nseq++; nlit += (u32)ll;
+                sink.push<G>(k, offBase, ll, lenA - 3);
                 ip0 = m_start + (int)lenA; anchor = ip0;
                 if (m_cur0 >= 0 && k == 0) {
                     // the pair's other position, if the match has not swallowed it; then the fill: the searched position + 2 and ip0 - 2
@@ -301,16 +276,9 @@ KX_DEV void zstd_match_fast_dict_body(const KFastDictArgs& d)
         // ================= finish the slice ==================================
         if (kx_any(state == KFD_CLEANUP)) {
             if (state == KFD_CLEANUP) {
-                {
-                    u32 const cnt = nseq & (2u * G - 1u);
-                    u64* const sp = (u64*)(seqs + (nseq - cnt));
-                    if (2u * (u32)k < cnt) sp[2 * k] = sq0;
-                    if (2u * (u32)k + 1u < cnt) sp[2 * k + 1] = sq1;
-                }
+                sink.flush<G>(k);
                 if (k == 0) {
-                    KSliceMeta mm;
-                    mm.nbSeq = nseq; mm.litSize = nlit; mm.lastLL = (u32)(n - anchor);
-                    mm.longType = longType; mm.longPos = longPos; mm.status = status; mm.pad[0] = 0; mm.pad[1] = 0;
+                    KSliceMeta mm = sink.meta((u32)(n - anchor), status);
                     a.meta[slice] = mm;
                 }
                 state = KFD_IDLE;
