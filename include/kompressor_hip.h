@@ -367,7 +367,8 @@ KMP_API int kmp_zstd_frame_info_batch(kmp_batch_ctx* ctx, const void* d_src, con
  * KMP_ERR_ARG), d_total[0] = the sum over all n: what the destination must hold, d_total[1] = the entries given capacity 0 for one of
  * the two reasons.  One kernel, asynchronous, deterministic; the arrays are what kmp_zstd_decompress_batch takes.  A caller reads
  * d_total[0] back once (the one host wait, forced by the allocation), or decodes into a destination it knows to be large enough
- * without any. */
+ * without any.  The kernel reads `bound` (offset 8) and `status` (offset 16, tested against 0) only: it takes a kmp_inflate_info
+ * array (below) by a pointer cast, for the layout of kmp_inflate_batch. */
 KMP_API int kmp_batch_layout(kmp_batch_ctx* ctx, const kmp_zstd_frame_info* d_info, uint32_t n, uint32_t align,
                              uint64_t* d_out_off, uint32_t* d_out_cap, uint64_t* d_total /* [2] */, void* hip_stream);
 /* The same inspection of entries in HOST memory: the same code compiled for the host, no GPU touched, no context needed (a batch of
@@ -438,6 +439,29 @@ KMP_API int kmp_inflate_batch(kmp_batch_ctx* ctx,
                               const void* d_src, const uint64_t* d_in_off, const uint32_t* d_in_len, uint32_t n,
                               void* d_dst, const uint64_t* d_out_off, const uint32_t* d_out_cap,
                               uint32_t* d_out_len, int32_t* d_status, int format, void* hip_stream);
+/* How large the entries of a batch of DEFLATE streams decode to, for callers who do not know (a DEFLATE stream declares no size: raw
+ * and zlib streams carry none, gzip's ISIZE stands at the end and is mod 2^32).  Entry i is walked block by block and Huffman code by
+ * Huffman code, a lane per stream -- stored, fixed and dynamic blocks, the zlib header, the gzip header with FEXTRA / FNAME / FCOMMENT /
+ * FHCRC --, nothing is written but d_info[i], and no byte outside the entry is read, whatever its bytes and wherever it lies.  Accepted
+ * is what zlib's inflate accepts as one complete stream that fills the entry (tests/golden/inflate_info_golden.json) -- except that
+ * the Adler-32 / CRC-32 VALUES of the trailers are NOT verified (there is no output to sum): kmp_inflate_batch, run afterwards,
+ * reports them.  gzip's ISIZE is checked against the size mod 2^32, and a header CRC (FHCRC) against the header. */
+typedef struct {
+    uint64_t content;   /* bytes the entry decodes to (may exceed 32 bits: 1 032 x the entry at most) */
+    uint64_t bound;     /* = content: what kmp_batch_layout reads */
+    int32_t  status;    /* 0, -3 (Z_DATA_ERROR) or -5 (Z_BUF_ERROR: the entry ends before its last block does, or is too short to hold
+                         * its wrapper: 6 bytes zlib, 18 gzip); then content = bound = 0, and so is every field below */
+    uint32_t blocks;    /* DEFLATE blocks walked */
+    uint32_t flags;     /* bit 0 a stored block, bit 1 a fixed-Huffman block, bit 2 a dynamic block, bit 3 the entry is gzip
+                         * (format 2, or 3 detected), bit 4 its gzip header has optional fields (FEXTRA / FNAME / FCOMMENT / FHCRC) */
+    uint32_t window_bits; /* zlib wrapper: CINFO + 8; otherwise 0 */
+} kmp_inflate_info;     /* 32 bytes; laid out so that kmp_batch_layout takes the array unchanged */
+/* format 0 .. 3 as in kmp_inflate_batch (else KMP_ERR_ARG).  d_info: device memory of the caller's, n entries, 8-byte aligned.  One
+ * kernel, asynchronous on hip_stream: no allocation, no host wait, nothing of the context's decode staging is touched (kmp_batch_memory
+ * answers the same before and after, on a context that has never decoded).  n up to the context's max_slices; n == 0 is KMP_OK.
+ * Then: kmp_batch_layout((const kmp_zstd_frame_info*)d_info, ...) -> d_out_off / d_out_cap -> kmp_inflate_batch. */
+KMP_API int kmp_inflate_info_batch(kmp_batch_ctx* ctx, const void* d_src, const uint64_t* d_in_off, const uint32_t* d_in_len, uint32_t n,
+                                   kmp_inflate_info* d_info, int format, void* hip_stream);
 /* ms4[0..3] = k_deflate_chains, k_deflate_best, k_deflate_parse, k_deflate_encode of the last batch */
 KMP_API int kmp_deflate_last_kernel_ms(kmp_batch_ctx* ctx, float* ms4);
 

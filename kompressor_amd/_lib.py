@@ -53,6 +53,7 @@ SIGNATURES = [
     ("kmp_deflate_compress_batch_params", _c.c_int, [_P, _P, _P, _P, _c.c_uint32, _P, _P, _P, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _P]),
     ("kmp_deflate_bound_params", _c.c_size_t, [_c.c_size_t, _c.c_int, _c.c_int]),
     ("kmp_inflate_batch", _c.c_int, [_P, _P, _P, _P, _c.c_uint32, _P, _P, _P, _P, _P, _c.c_int, _P]),
+    ("kmp_inflate_info_batch", _c.c_int, [_P, _P, _P, _P, _c.c_uint32, _P, _c.c_int, _P]),
     ("kmp_deflate_last_kernel_ms", _c.c_int, [_P, _c.POINTER(_c.c_float)]),
     ("kmp_zlib_create_compressor", _P, [_c.c_int, _c.c_int, _c.c_int, _c.c_int]),
     ("kmp_zlib_free_compressor", _c.c_int, [_P]),

@@ -338,11 +338,40 @@ class ZstdBatch:
 
     _FORMATS = {"raw": 0, "zlib": 1, "gzip": 2, "auto": 3}
 
-    def inflate(self, src, in_off, in_len, out_cap, zlib_wrapper=False, dst=None, out_off=None, format=None):   # noqa: A002
+    def _inflate_info_raw(self, src, in_off, in_len, fmt):
+        """kmp_inflate_info_batch -> the n x 32 bytes of kmp_inflate_info as an int64 tensor of n x 4 (queued, no host wait)"""
+        n = in_len.numel()
+        info = torch.empty((n, 4), dtype=torch.int64, device=self.device)
+        rc = self.lib.kmp_inflate_info_batch(self._h, _ptr(src), _ptr(in_off), _ptr(in_len), n, _ptr(info), fmt, self._stream())
+        if rc != 0:
+            raise RuntimeError(f"kmp_inflate_info_batch failed ({rc}): {self._err()}")
+        return info
+
+    def inflate_info(self, src, in_off, in_len, format="raw"):   # noqa: A002
+        """How large each DEFLATE stream decodes to, walked on the device without decoding (kmp_inflate_info_batch; no host wait).
+        Returns a dict of device tensors over the n entries (views of one buffer): content and bound (int64, equal), status (int32:
+        0, -3 or -5; then every other field is 0), blocks, flags (bit 0 a stored block, 1 a fixed one, 2 a dynamic one, 3 gzip, 4 a
+        gzip header with optional fields), window_bits (int32).  The trailers' Adler-32 / CRC-32 values are not verified: inflate
+        reports them."""
+        info = self._inflate_info_raw(src, in_off, in_len, self._FORMATS[format])
+        w = info.view(torch.int32)                      # n x 8 words
+        return {"content": info[:, 0], "bound": info[:, 1], "status": w[:, 4], "blocks": w[:, 5], "flags": w[:, 6], "window_bits": w[:, 7]}
+
+    def inflate(self, src, in_off, in_len, out_cap=None, zlib_wrapper=False, dst=None, out_off=None, format=None, align=1):   # noqa: A002
         """n DEFLATE streams -> slices; format "raw" / "zlib" / "gzip" / "auto" (zlib or gzip per stream).
-        Returns (dst, out_off, out_len, status)."""
+        Returns (dst, out_off, out_len, status).
+        out_cap=None: the sizes are found on the device (inflate_info, then layout with `align`: a power of two up to 4096 that every
+        out_off is a multiple of); the one host wait is reading the total back to allocate dst.  An entry the sizing pass rejects (or
+        that decodes to 4 GiB or more) gets capacity 0, and the decoder's own status for it is nonzero."""
         fmt = self._FORMATS[format] if format is not None else (1 if zlib_wrapper else 0)
         n = in_len.numel()
+        if out_cap is None:
+            if dst is not None or out_off is not None:
+                raise ValueError("out_cap=None lays the destination out itself: pass neither dst nor out_off")
+            out_off, out_cap, total = self.layout(self._inflate_info_raw(src, in_off, in_len, fmt), align)
+            dst = torch.empty(int(total[0].item()) + 64, dtype=torch.uint8, device=self.device)
+        elif align != 1:
+            raise ValueError("align belongs to out_cap=None (with out_cap given, out_off is the caller's)")
         if out_off is None:
             out_off = torch.cumsum(out_cap.to(torch.int64), 0) - out_cap.to(torch.int64)
         if dst is None:

@@ -8,6 +8,7 @@
 #include "deflate_encode.h"
 #include "deflate_decode.h"
 #include "deflate_predecode.h"
+#include "deflate_info.h"
 #include "kmp_internal.h"
 
 __global__ __launch_bounds__(256) void k_deflate_chains(KdArgs a) { deflate_chains_body<u16>(a); }          // slices <= 64 KiB
@@ -33,6 +34,7 @@ __global__ __launch_bounds__(256) void k_max_len(const u32* len, u32 n, u32* out
 __global__ __launch_bounds__(64, 8) void k_deflate_lazy(KdArgs a) { deflate_lazy_body<false>(a); }
 __global__ __launch_bounds__(64, 2) void k_inflate_predecode(KipArgs a) { inflate_predecode_body(a); }
 __global__ __launch_bounds__(64) void k_inflate_exec(KieArgs a) { inflate_exec_body(a); }
+__global__ __launch_bounds__(64, 2) void k_inflate_size(KisArgs a) { inflate_size_body(a); }                // sizes only, a lane per stream (deflate_info.h)
 __global__ __launch_bounds__(64, 4) void k_deflate_encode(KdArgs a) { deflate_encode_body(a); }
 __global__ __launch_bounds__(64, 5) void k_inflate(KiArgs a) { inflate_body(a); }
 
@@ -82,6 +84,23 @@ extern "C" int kmp_inflate_batch(kmp_batch_ctx* c, const void* d_src, const uint
                                  void* d_dst, const uint64_t* d_out_off, const uint32_t* d_out_cap, uint32_t* d_out_len, int32_t* d_status,
                                  int format, void* hip_stream)
 { return inflate_batch_impl(c, d_src, d_in_off, d_in_len, n, d_dst, d_out_off, d_out_cap, d_out_len, d_status, format, 0, hip_stream); }
+
+// The sizing pass: like the zstd frame inspection it allocates nothing, waits for nothing and touches nothing of the context's
+// decode staging (no batch_begin: the context gives its device and max_slices).  The entries are walked in the caller's order:
+// the size sort of inflate_batch_impl keeps its keys in the staging, which this call must leave alone.
+extern "C" int kmp_inflate_info_batch(kmp_batch_ctx* c, const void* d_src, const uint64_t* d_in_off, const uint32_t* d_in_len, uint32_t n,
+                                      kmp_inflate_info* d_info, int format, void* hip_stream)
+{
+    if (format < 0 || format > 3) { g_last_error = "kmp_inflate_info_batch: format must be 0 (raw), 1 (zlib), 2 (gzip) or 3 (zlib or gzip)"; return KMP_ERR_ARG; }
+    KMP_TRY(batch_args("kmp_inflate_info_batch", c, n, { d_src, d_in_off, d_in_len, d_info }));
+    if (n == 0) return KMP_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    KisArgs a;
+    a.src = (const u8*)d_src; a.in_off = d_in_off; a.in_len = d_in_len; a.n_slices = n; a.info = d_info; a.format = (u32)format;
+    hipLaunchKernelGGL(k_inflate_size, dim3((n + KIP_STREAMS - 1) / KIP_STREAMS), dim3(64), 0, (hipStream_t)hip_stream, a);
+    HIP_TRY(hipGetLastError());
+    return KMP_OK;
+}
 
 // window_bits: what the caller declared to inflateInit2 (8 .. 15; 0 = 15): zlib streams whose header names a larger window are refused
 int inflate_batch_impl(kmp_batch_ctx* c, const void* d_src, const uint64_t* d_in_off, const uint32_t* d_in_len, uint32_t n,
