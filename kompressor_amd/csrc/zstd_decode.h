@@ -15,6 +15,7 @@
 // literal and match copies cooperatively.
 #pragma once
 #include "zstd_common.h"
+#include "zstd_format.h"
 
 // What k_zstd_seq_predecode (zstd_predecode.h: one lane per frame) leaves for a compressed block of an entry's first
 // frame: where its decoded sequences (litLength, matchLength, offset) start in the entry's staging area, how many, whether
@@ -640,51 +641,40 @@ KX_DEV void zstd_decode_frame(const KDecodeArgs& a, KDecodeLds& lds, u32 f, int 
     bool const seqAll = (npreW >> 31) != 0, litAll = (nlitW >> 31) != 0;
     for (;;) {
     // ---- frame header (every lane computes the same thing) ---------------
-    u32 hasContent = 0, checksum = 0; u64 contentSize = 0; u64 windowSize = 0;
-    u32 const fstart = pos, fbase = op;       // this frame's first input byte / first output byte
+    u32 hasContent = 0, checksum = 0; u64 contentSize = 0;
+    u32 const fbase = op;                     // this frame's first output byte
     if (srcSize - pos < 5) { if (srcSize != pos) err = KZE_SRCSIZE; break; }      // an empty entry decodes to nothing, as ZSTD_decompress has it
     {
         u32 const magic = kx_ld32(src + pos);
-        if ((magic & 0xFFFFFFF0u) == 0x184D2A50u) {                // skippable frame: magic, 4-byte size, payload
+        if ((magic & ZF_SKIP_MASK) == ZF_SKIP_MAGIC) {                // skippable frame: magic, 4-byte size, payload
             if (srcSize - pos < 8) { err = KZE_SRCSIZE; break; }
             u32 const sz = kx_ld32(src + pos + 4);
             if (sz > srcSize - pos - 8) { err = KZE_SRCSIZE; break; }
             pos += 8 + sz; nframes++;
             continue;
         }
-        if (magic != 0xFD2FB528u) { err = nframes ? KZE_SRCSIZE : KZE_PREFIX; break; }   // garbage after a complete frame: "Src size is incorrect"
+        if (magic != ZF_MAGIC) { err = nframes ? KZE_SRCSIZE : KZE_PREFIX; break; }   // garbage after a complete frame: "Src size is incorrect"
     }
     {
-        u32 const fhd = src[pos + 4]; u32 const dictId = fhd & 3, single = (fhd >> 5) & 1, fcsId = fhd >> 6;
-        checksum = (fhd >> 2) & 1;
-        if (fhd & 0x08) err = KZE_FRAMEPARAM;
+        // (the reserved bit is looked at before the header's length: libzstd has it the other way round)
+        ZfDescriptor const fd = zf_descriptor(src[pos + 4]);
+        checksum = fd.checksum;
+        if (fd.reserved) err = KZE_FRAMEPARAM;
+        if (!err && fd.header_size > srcSize - pos) err = KZE_SRCSIZE;
         pos += 5;
-        u32 const didSize = dictId == 3 ? 4 : dictId;
-        u32 const fcsSize = fcsId == 0 ? single : (fcsId == 1 ? 2 : fcsId == 2 ? 4 : 8);
-        if (!err && pos + (single ? 0u : 1u) + didSize + fcsSize > srcSize) err = KZE_SRCSIZE;
-        if (!err && !single) {
-            u32 const wd = src[pos++]; u32 const wlog = 10 + (wd >> 3);
-            if (wlog > 31) err = KZE_WINDOW;
-            else { windowSize = 1ull << wlog; windowSize += (windowSize >> 3) * (wd & 7); }
-        }
+        if (!err && !fd.single) { if (zf_window(src[pos]).log > 31) err = KZE_WINDOW; pos++; }
         if (!err) {
-            u32 did = 0;
-            for (u32 i = 0; i < didSize; i++) did |= (u32)src[pos + i] << (8 * i);
+            u32 const did = (u32)zf_le(src + pos, fd.did_bytes);
             if (did && did != a.dict_id) err = KZE_DICT;           // "Dictionary mismatch" (a header without an ID takes whatever dictionary is loaded)
-            pos += didSize;
-            if (fcsSize) {
+            pos += fd.did_bytes;
+            if (fd.fcs_bytes) {
                 hasContent = 1;
-                if (fcsSize == 1) contentSize = src[pos];
-                else if (fcsSize == 2) contentSize = (u64)kx_ld16(src + pos) + 256;
-                else if (fcsSize == 4) contentSize = kx_ld32(src + pos);
-                else contentSize = kx_ld64(src + pos);
-                pos += fcsSize;
-                if (single) windowSize = contentSize;
+                contentSize = zf_content_size(src + pos, fd.fcs_bytes);
+                pos += fd.fcs_bytes;
                 if (!err && contentSize > cap - op) err = KZE_DSTSMALL;
             }
         }
     }
-    (void)fstart; (void)windowSize;
 
     // ---- blocks -----------------------------------------------------------
     u32 rep1 = 1, rep2 = 4, rep3 = 8;
@@ -704,8 +694,8 @@ KX_DEV void zstd_decode_frame(const KDecodeArgs& a, KDecodeLds& lds, u32 f, int 
     bool last = false;
     while (!err && !last) {
         if (pos + 3 > srcSize) { err = KZE_SRCSIZE; break; }
-        u32 const bh = (u32)src[pos] | ((u32)src[pos + 1] << 8) | ((u32)src[pos + 2] << 16);
-        last = bh & 1; u32 const btype = (bh >> 1) & 3; u32 const bsize = bh >> 3;
+        ZfBlock const bh = zf_block(src + pos);
+        last = bh.last; u32 const btype = bh.type, bsize = bh.size;
         pos += 3;
         if (btype == 3) { err = KZE_CORRUPT; break; }
         if (btype == 0) {
@@ -725,24 +715,14 @@ KX_DEV void zstd_decode_frame(const KDecodeArgs& a, KDecodeLds& lds, u32 f, int 
         }
         // ---- compressed block --------------------------------------------
         u32 const ord = (nframes == 0) ? cblk++ : 0xFFFFFFFFu;          // index into what the pre-decode kernels left for the entry's first frame
-        if (pos + bsize > srcSize || bsize > 128u * 1024u) { err = KZE_SRCSIZE; break; }     // libzstd: "Src size is incorrect" for both
+        if (pos + bsize > srcSize || bsize > ZF_BLOCK_MAX) { err = KZE_SRCSIZE; break; }     // libzstd: "Src size is incorrect" for both
         if (bsize < 2) { err = KZE_CORRUPT; break; }
         const u8* const bp = src + pos; u32 const bend = bsize;
-        // literals section header
-        u32 const lh0 = bp[0]; u32 const ltype = lh0 & 3, sf = (lh0 >> 2) & 3;
-        u32 lhSize, regen, comp = 0, nstreams = 1;
-        if (ltype < 2) {
-            if (sf == 0 || sf == 2) { lhSize = 1; regen = lh0 >> 3; }
-            else if (sf == 1) { lhSize = 2; regen = kx_ld16(bp) >> 4; }
-            else { lhSize = 3; regen = ((u32)bp[0] | ((u32)bp[1] << 8) | ((u32)bp[2] << 16)) >> 4; }
-        } else {
-            if (bend < 5) { err = KZE_CORRUPT; break; }
-            u32 const w = kx_ld32(bp);
-            if (sf < 2) { lhSize = 3; regen = (w >> 4) & 0x3FF; comp = (w >> 14) & 0x3FF; nstreams = sf ? 4 : 1; }
-            else if (sf == 2) { lhSize = 4; regen = (w >> 4) & 0x3FFF; comp = w >> 18; nstreams = 4; }
-            else { lhSize = 5; regen = (w >> 4) & 0x3FFFF; comp = (w >> 22) + ((u32)bp[4] << 10); nstreams = 4; }
-        }
-        if (regen > 128u * 1024u) { err = KZE_CORRUPT; break; }
+        // literals section header: one that does not fit its block is corrupt, whatever lies behind the block
+        ZfLiterals const lh = zf_literals(bp, bend);
+        if (!lh.fits) { err = KZE_CORRUPT; break; }
+        u32 const ltype = lh.type, lhSize = lh.header, regen = lh.regen, comp = lh.comp, nstreams = lh.streams;
+        if (regen > ZF_BLOCK_MAX) { err = KZE_CORRUPT; break; }
         // the literal buffer belongs to a context created for smaller slices: not the frame's fault (raw literals are read in place)
         if (ltype != 0 && regen > a.lit_cap) { err = KZE_WORKSPACE; break; }
         const u8* litPtr = lits; u32 lpos = lhSize;
@@ -804,22 +784,9 @@ KX_DEV void zstd_decode_frame(const KDecodeArgs& a, KDecodeLds& lds, u32 f, int 
         }
         kx_sync();
         // sequences header (every lane computes the same thing), then the three tables (lane 0)
-        u32 nbSeq = 0, spos = lpos, modes = 0;
-        {
-            u32 e = 0;
-            if (spos >= bend) e = KZE_CORRUPT;
-            if (!e) {
-                u32 const b0 = bp[spos++];
-                if (b0 < 128) nbSeq = b0;
-                else if (b0 < 255) { if (spos >= bend) e = KZE_CORRUPT; else nbSeq = ((b0 - 128) << 8) + bp[spos++]; }
-                else { if (spos + 2 > bend) e = KZE_CORRUPT; else { nbSeq = kx_ld16(bp + spos) + 0x7F00; spos += 2; } }
-            }
-            if (!e && nbSeq) {
-                if (spos >= bend) e = KZE_CORRUPT;
-                else { modes = bp[spos++]; if (modes & 3) e = KZE_CORRUPT; }
-            }
-            if (e) { err = e; break; }
-        }
+        ZfSequences const sh = zf_sequences(bp, lpos, bend);
+        if (!sh.have_count || (sh.count && (!sh.have_modes || (sh.modes & 3)))) { err = KZE_CORRUPT; break; }
+        u32 const nbSeq = sh.count, modes = sh.modes; u32 spos = sh.next;
         // this block's sequences may lie decoded in HBM already (k_zstd_seq_predecode)
         const u64* preSeq = nullptr; u32 preRep1 = 0, preRep2 = 0, preRep3 = 0;
         if (ord < npre) {

@@ -3,35 +3,28 @@
 // kmp_zstd_frame_info_host) and the layout a decode needs made of the answers (kmp_batch_layout).
 //
 // kx_frame_info is ONE body compiled three ways: by hipcc for the kernel, by hipcc's host pass for the host call and by g++ for the
-// emulator and the stand-alone sanitizer program (tests/emu/): it needs <stdint.h> and the public header only.  It restates the walk
-// of libzstd 1.5.7 (lib/decompress/zstd_decompress.c: ZSTD_findFrameSizeInfo, ZSTD_getFrameHeader_advanced, readSkippableFrameSize,
+// emulator and the stand-alone sanitizer program (tests/emu/): it needs <stdint.h>, the public header and zstd_format.h.  It restates the walk of
+// libzstd 1.5.7 (lib/decompress/zstd_decompress.c: ZSTD_findFrameSizeInfo, ZSTD_getFrameHeader_advanced, readSkippableFrameSize,
 // ZSTD_getcBlockSize) in that library's order of checks, because the order decides which error a damaged entry gets:
 //   fewer than 5 bytes          72 when they are a prefix of the zstd magic or of a skippable magic (low nibble free), else 10
 //   skippable magic, < 8 bytes  72;  size + 8 wraps 32 bits: 14;  size + 8 beyond the entry: 72
 //   another magic               10  (0xFD2FB525 .. 27, the formats of zstd 0.5 .. 0.7, are known to the library: below)
 //   header longer than entry    72  -- before the reserved bit (14) and the window (16: a window log above 31) are looked at
 //   block header cut short      72;  block type 3: 20;  block beyond the entry: 72;  checksum cut short: 72
-// Every byte is read with a byte load below an explicit bound: nothing outside [src, src + len) is touched, wherever the entry lies.
+// Every read lies below an explicit bound: nothing outside [src, src + len) is touched, wherever the entry lies.
 //
 // The kernel bodies (zstd_frame_info_body, batch_layout_body) follow under KX_DEV: they are written against kx_wave.h, which the
 // includer brings (the product's or the emulator's).
 #pragma once
 #include <stdint.h>
 #include "../../include/kompressor_hip.h"
-
-#if defined(__HIPCC__)
-#define KFI_HD __host__ __device__ inline
-#else
-#define KFI_HD static inline
-#endif
+#include "zstd_format.h"
 
 #define KFI_CONTENT_ERROR (~0ull - 1)          // ZSTD_CONTENTSIZE_ERROR: what the library's size functions answer for a total they cannot give
 
-KFI_HD uint32_t kfi_le32(const uint8_t* p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24); }
-
 // One entry, frame by frame.  Fields as include/kompressor_hip.h documents them; frames / dict_id / flags cover the frames in front of
 // the first one that is rejected.
-KFI_HD void kx_frame_info(const uint8_t* src, uint32_t len, kmp_zstd_frame_info* out)
+ZF_HD void kx_frame_info(const uint8_t* src, uint32_t len, kmp_zstd_frame_info* out)
 {
     uint64_t content = 0, bound = 0;
     uint32_t status = 0, frames = 0, dict_id = 0, flags = 0;
@@ -39,10 +32,10 @@ KFI_HD void kx_frame_info(const uint8_t* src, uint32_t len, kmp_zstd_frame_info*
     while (pos < len) {
         const uint8_t* const p = src + pos;
         uint32_t const rem = len - pos;
-        if (rem >= 4 && kfi_le32(p) - 0xFD2FB525u <= 2u) {
+        if (rem >= 4 && zf_ld32(p) - 0xFD2FB525u <= 2u) {
             // The binary library carries the frame formats of zstd 0.5, 0.6 and 0.7 (ZSTD_LEGACY_SUPPORT 5) and sizes their frames too
             // (ZSTDv05/06/07_findFrameSizeInfoLegacy, ZSTD_getDecompressedSize_legacy).  The decoders here do not decode them: flags bit 2.
-            uint32_t const v = kfi_le32(p) - 0xFD2FB520u;
+            uint32_t const v = zf_ld32(p) - 0xFD2FB520u;
             if (rem < (v == 7u ? 8u : 5u)) { status = 72; break; }
             uint32_t const d = p[4];
             uint32_t const fcs_code = d >> 6;
@@ -95,67 +88,52 @@ KFI_HD void kx_frame_info(const uint8_t* src, uint32_t len, kmp_zstd_frame_info*
         if (rem < 5) {
             // ZSTD_getFrameHeader: the bytes present laid over the zstd magic, then over the first skippable magic
             uint32_t const n = rem < 4 ? rem : 4;
-            uint32_t a = 0xFD2FB528u, b = 0x184D2A50u;
+            uint32_t a = ZF_MAGIC, b = ZF_SKIP_MAGIC;
             for (uint32_t k = 0; k < n; k++) {
                 uint32_t const m = 0xFFu << (8 * k), v = (uint32_t)p[k] << (8 * k);
                 a = (a & ~m) | v; b = (b & ~m) | v;
             }
-            status = (a == 0xFD2FB528u || (b & 0xFFFFFFF0u) == 0x184D2A50u) ? 72u : 10u;
+            status = (a == ZF_MAGIC || (b & ZF_SKIP_MASK) == ZF_SKIP_MAGIC) ? 72u : 10u;
             break;
         }
-        uint32_t const magic = kfi_le32(p);
-        if ((magic & 0xFFFFFFF0u) == 0x184D2A50u) {
+        uint32_t const magic = zf_ld32(p);
+        if ((magic & ZF_SKIP_MASK) == ZF_SKIP_MAGIC) {
             if (rem < 8) { status = 72; break; }
-            uint32_t const sz = kfi_le32(p + 4);
+            uint32_t const sz = zf_ld32(p + 4);
             if ((uint32_t)(sz + 8u) < sz) { status = 14; break; }
             if (sz + 8u > rem) { status = 72; break; }
             pos += sz + 8u;
             flags |= 2u;
             continue;
         }
-        if (magic != 0xFD2FB528u) { status = 10; break; }
-        uint32_t const fhd = p[4];
-        uint32_t const did_code = fhd & 3u, single = (fhd >> 5) & 1u, fcs_code = fhd >> 6;
-        uint32_t const did_bytes = did_code == 3 ? 4u : did_code;
-        uint32_t const fcs_bytes = fcs_code ? 1u << fcs_code : single;
-        uint32_t const hsize = 5u + (single ^ 1u) + did_bytes + fcs_bytes;          // 6 .. 18
-        if (rem < hsize) { status = 72; break; }
-        if (fhd & 8u) { status = 14; break; }
-        uint32_t q = 5;
-        uint64_t window = 0;
-        if (!single) {
-            uint32_t const wl = p[q++];
-            uint32_t const wlog = (wl >> 3) + 10u;
-            if (wlog > 31u) { status = 16; break; }
-            window = 1ull << wlog;
-            window += (window >> 3) * (wl & 7u);
+        if (magic != ZF_MAGIC) { status = 10; break; }
+        ZfDescriptor const fd = zf_descriptor(p[4]);
+        if (rem < fd.header_size) { status = 72; break; }
+        if (fd.reserved) { status = 14; break; }
+        uint32_t q = 5; uint64_t window = 0;
+        if (!fd.single) {
+            ZfWindow const w = zf_window(p[q++]);
+            if (w.log > 31u) { status = 16; break; }
+            window = w.size;
         }
-        uint32_t did = 0;
-        for (uint32_t k = 0; k < did_bytes; k++) did |= (uint32_t)p[q + k] << (8 * k);
-        q += did_bytes;
-        uint64_t fcs = ~0ull;
-        if (fcs_bytes) {
-            fcs = 0;
-            for (uint32_t k = 0; k < fcs_bytes; k++) fcs |= (uint64_t)p[q + k] << (8 * k);
-            if (fcs_code == 1) fcs += 256;
-        }
-        if (single) window = fcs;
-        uint64_t const block_max = window < (128u << 10) ? window : (uint64_t)(128u << 10);
+        uint32_t const did = (uint32_t)zf_le(p + q, fd.did_bytes); q += fd.did_bytes;
+        uint64_t const fcs = fd.fcs_bytes ? zf_content_size(p + q, fd.fcs_bytes) : ~0ull;
+        if (fd.single) window = fcs;
+        uint64_t const block_max = window < ZF_BLOCK_MAX ? window : (uint64_t)ZF_BLOCK_MAX;
         // the blocks: 3 header bytes each, then the block's bytes (an RLE block: one)
-        uint32_t at = hsize, blocks = 0;
+        uint32_t at = fd.header_size, blocks = 0;
         for (;;) {
             if (rem - at < 3u) { status = 72; break; }
-            uint32_t const bh = (uint32_t)p[at] | ((uint32_t)p[at + 1] << 8) | ((uint32_t)p[at + 2] << 16);
-            uint32_t const type = (bh >> 1) & 3u;
-            if (type == 3u) { status = 20; break; }
-            uint32_t const csize = type == 1u ? 1u : bh >> 3;
+            ZfBlock const bh = zf_block(p + at);
+            if (bh.type == 3u) { status = 20; break; }
+            uint32_t const csize = bh.type == 1u ? 1u : bh.size;
             if (3u + csize > rem - at) { status = 72; break; }
             at += 3u + csize;
             blocks++;
-            if (bh & 1u) break;
+            if (bh.last) break;
         }
         if (status) break;
-        if (fhd & 4u) {
+        if (fd.checksum) {
             if (rem - at < 4u) { status = 72; break; }
             at += 4u;
         }
@@ -166,7 +144,7 @@ KFI_HD void kx_frame_info(const uint8_t* src, uint32_t len, kmp_zstd_frame_info*
         if (content < KFI_CONTENT_ERROR) content = fcs >= KFI_CONTENT_ERROR ? fcs : content + fcs < content ? KFI_CONTENT_ERROR : content + fcs;
         if (!frames) dict_id = did;
         frames++;
-        if (fhd & 4u) flags |= 1u;
+        if (fd.checksum) flags |= 1u;
         pos += at;
     }
     if (status) { content = 0; bound = 0; }

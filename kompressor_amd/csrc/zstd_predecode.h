@@ -117,41 +117,21 @@ struct KSeqSortArgs { const u8* src; const u64* in_off; const u32* in_len; u32 n
 // sequences of the entry's first compressed block; 0 when there is none or anything is irregular (the pre-decoder will see that itself)
 KX_DEV u32 kxp_first_nbseq(const u8* src, u32 srcSize)
 {
-    if (srcSize < 9 || kx_ld32(src) != 0xFD2FB528u) return 0;
-    u32 const fhd = src[4]; u32 const dictId = fhd & 3, single = (fhd >> 5) & 1, fcsId = fhd >> 6;
-    u32 const didSize = dictId == 3 ? 4 : dictId;
-    u32 const fcsSize = fcsId == 0 ? single : (fcsId == 1 ? 2 : fcsId == 2 ? 4 : 8);
-    u32 pos = 5 + (single ? 0u : 1u) + didSize + fcsSize;
+    if (srcSize < 9 || kx_ld32(src) != ZF_MAGIC) return 0;
+    u32 pos = zf_descriptor(src[4]).header_size;
     for (int guard = 0; guard < 4; guard++) {                   // raw / RLE blocks in front of it: a few at most are followed
         if (pos + 3 > srcSize) return 0;
-        u32 const bh = (u32)src[pos] | ((u32)src[pos + 1] << 8) | ((u32)src[pos + 2] << 16);
-        u32 const btype = (bh >> 1) & 3, bsize = bh >> 3;
+        ZfBlock const bh = zf_block(src + pos);
         pos += 3;
-        if (btype == 2) {
-            if (pos + bsize > srcSize || bsize < 5) return 0;
+        if (bh.type == 2) {
+            if (pos + bh.size > srcSize || bh.size < 5) return 0;
             const u8* const bp = src + pos;
-            u32 const lh0 = bp[0]; u32 const ltype = lh0 & 3, sf = (lh0 >> 2) & 3; u32 lpos;
-            if (ltype < 2) {
-                u32 lhSize, regen;
-                if (sf == 0 || sf == 2) { lhSize = 1; regen = lh0 >> 3; }
-                else if (sf == 1) { lhSize = 2; regen = kx_ld16(bp) >> 4; }
-                else { lhSize = 3; regen = ((u32)bp[0] | ((u32)bp[1] << 8) | ((u32)bp[2] << 16)) >> 4; }
-                lpos = lhSize + (ltype == 0 ? regen : 1u);
-            } else {
-                u32 const w = kx_ld32(bp); u32 lhSize, comp;
-                if (sf < 2) { lhSize = 3; comp = (w >> 14) & 0x3FF; }
-                else if (sf == 2) { lhSize = 4; comp = w >> 18; }
-                else { lhSize = 5; comp = (w >> 22) + ((u32)bp[4] << 10); }
-                lpos = lhSize + comp;
-            }
-            if (lpos + 3 > bsize) return 0;
-            u32 const b0 = bp[lpos];
-            if (b0 < 128) return b0;
-            if (b0 < 255) return ((b0 - 128) << 8) + bp[lpos + 1];
-            return kx_ld16(bp + lpos + 1) + 0x7F00;
+            ZfLiterals const lh = zf_literals(bp, bh.size);          // (five bytes: whatever the header is, it fits)
+            if (lh.section + 3 > bh.size) return 0;
+            return zf_sequences(bp, lh.section, bh.size).count;      // (three bytes: so does the count)
         }
-        if (btype == 3 || (bh & 1)) return 0;
-        pos += btype == 0 ? bsize : 1u;
+        if (bh.type == 3 || bh.last) return 0;
+        pos += bh.type == 0 ? bh.size : 1u;
     }
     return 0;
 }
@@ -208,14 +188,11 @@ KX_DEV void zstd_seq_predecode_body(const KPreArgs& a)
     u32 nb = 0, nstaged = 0;              // compressed blocks seen / sequences staged so far
     u32 pos = 0;
     // ---- frame header (first frame of the entry only) ----
-    bool ok = srcSize >= 5 && kx_ld32(src) == 0xFD2FB528u;
+    bool ok = srcSize >= 5 && kx_ld32(src) == ZF_MAGIC;
     if (ok) {
-        u32 const fhd = src[4]; u32 const dictId = fhd & 3, single = (fhd >> 5) & 1, fcsId = fhd >> 6;
-        if (fhd & 0x08) ok = false;
-        u32 const didSize = dictId == 3 ? 4 : dictId;
-        u32 const fcsSize = fcsId == 0 ? single : (fcsId == 1 ? 2 : fcsId == 2 ? 4 : 8);
-        pos = 5 + (single ? 0u : 1u) + didSize + fcsSize;
-        if (pos > srcSize) ok = false;
+        ZfDescriptor const fd = zf_descriptor(src[4]);
+        pos = fd.header_size;
+        if (fd.reserved || pos > srcSize) ok = false;
     }
     u32 rep1 = a.rep[0], rep2 = a.rep[1], rep3 = a.rep[2];
     u32 kind[3] = { 0, 0, 0 }, klog[3] = { 0, 0, 0 };        // (lane 0 of the quad)
@@ -223,45 +200,25 @@ KX_DEV void zstd_seq_predecode_body(const KPreArgs& a)
     u32 covered = 0;                      // set when the frame's last block has been taken: every compressed block has a record
     while (ok && !last && nb < a.blk_cap) {
         if (pos + 3 > srcSize) break;
-        u32 const bh = (u32)src[pos] | ((u32)src[pos + 1] << 8) | ((u32)src[pos + 2] << 16);
-        last = bh & 1; u32 const btype = (bh >> 1) & 3; u32 const bsize = bh >> 3;
+        ZfBlock const bh = zf_block(src + pos);
+        last = bh.last; u32 const btype = bh.type, bsize = bh.size;
         pos += 3;
         if (btype == 3) break;
         if (btype == 0) { if (pos + bsize > srcSize) break; pos += bsize; if (last) covered = 0x80000000u; continue; }
         if (btype == 1) { if (pos + 1 > srcSize) break; pos += 1; if (last) covered = 0x80000000u; continue; }
-        if (pos + bsize > srcSize || bsize > 128u * 1024u || bsize < 2) break;
+        if (pos + bsize > srcSize || bsize > ZF_BLOCK_MAX || bsize < 2) break;
         const u8* const bp = src + pos; u32 const bend = bsize;
         // literals section: only its size matters here
-        u32 const lh0 = bp[0]; u32 const ltype = lh0 & 3, sf = (lh0 >> 2) & 3;
-        u32 lpos;
-        if (ltype < 2) {
-            u32 lhSize, regen;
-            if (sf == 0 || sf == 2) { lhSize = 1; regen = lh0 >> 3; }
-            else if (sf == 1) { lhSize = 2; regen = kx_ld16(bp) >> 4; }
-            else { if (bend < 3) break; lhSize = 3; regen = ((u32)bp[0] | ((u32)bp[1] << 8) | ((u32)bp[2] << 16)) >> 4; }
-            lpos = lhSize + (ltype == 0 ? regen : 1u);
-        } else {
-            if (bend < 5) break;
-            u32 const w = kx_ld32(bp); u32 lhSize, comp;
-            if (sf < 2) { lhSize = 3; comp = (w >> 14) & 0x3FF; }
-            else if (sf == 2) { lhSize = 4; comp = w >> 18; }
-            else { lhSize = 5; comp = (w >> 22) + ((u32)bp[4] << 10); }
-            lpos = lhSize + comp;
-        }
-        if (lpos >= bend) break;
+        ZfLiterals const lh = zf_literals(bp, bend);
+        if (!lh.fits) break;
         // sequences header
-        u32 nbSeq, p2 = lpos;
-        {
-            u32 const b0 = bp[p2++];
-            if (b0 < 128) nbSeq = b0;
-            else if (b0 < 255) { if (p2 >= bend) break; nbSeq = ((b0 - 128) << 8) + bp[p2++]; }
-            else { if (p2 + 2 > bend) break; nbSeq = kx_ld16(bp + p2) + 0x7F00; p2 += 2; }
-        }
+        ZfSequences const sh = zf_sequences(bp, lh.section, bend);
+        if (!sh.have_count) break;
+        u32 const nbSeq = sh.count; u32 p2 = sh.next;
         KPreBlk rec; rec.seq_off = nstaged; rec.nbSeq = nbSeq; rec.ok = 0; rec.rep[0] = rep1; rec.rep[1] = rep2; rec.rep[2] = rep3; rec.pad[0] = 0; rec.pad[1] = 0;
         if (nbSeq == 0) { rec.ok = 1; if (role == 0) blk[nb] = rec; nb++; pos += bsize; if (last) covered = 0x80000000u; continue; }
-        if (p2 >= bend) break;
-        u32 const modes = bp[p2++];
-        if (modes & 3) break;
+        if (!sh.have_modes || (sh.modes & 3)) break;
+        u32 const modes = sh.modes;
         if (nstaged + nbSeq > a.seq_cap) break;
         u32 tlLL = 0, tlOF = 0, tlML = 0; bool tok = true;
         for (int t = 0; t < 3 && tok; t++) {
@@ -560,14 +517,11 @@ KX_DEV void zstd_lit_predecode_body(const KLitArgs& a)
         u32 covered = 0;                  // set when the frame's last block has been taken: every compressed block has a record
         if (owner) {
             srcA = a.src + a.in_off[fa]; srcSize = a.in_len[fa];
-            go = srcSize >= 5 && kx_ld32(srcA) == 0xFD2FB528u;
+            go = srcSize >= 5 && kx_ld32(srcA) == ZF_MAGIC;
             if (go) {
-                u32 const fhd = srcA[4]; u32 const dictId = fhd & 3, single = (fhd >> 5) & 1, fcsId = fhd >> 6;
-                if (fhd & 0x08) go = false;
-                u32 const didSize = dictId == 3 ? 4 : dictId;
-                u32 const fcsSize = fcsId == 0 ? single : (fcsId == 1 ? 2 : fcsId == 2 ? 4 : 8);
-                pos = 5 + (single ? 0u : 1u) + didSize + fcsSize;
-                if (pos > srcSize) go = false;
+                ZfDescriptor const fd = zf_descriptor(srcA[4]);
+                pos = fd.header_size;
+                if (fd.reserved || pos > srcSize) go = false;
             }
         }
         // ---- the decoding identity of every lane: stream sB of frame base + jB ----
@@ -586,23 +540,20 @@ KX_DEV void zstd_lit_predecode_body(const KLitArgs& a)
                 KLitFrameLds& L = lds.f[tid];
                 while (go && !last && !found) {
                     if (nb >= a.blk_cap || pos + 3 > srcSize) { go = false; break; }
-                    u32 const bh = (u32)srcA[pos] | ((u32)srcA[pos + 1] << 8) | ((u32)srcA[pos + 2] << 16);
-                    last = bh & 1; u32 const btype = (bh >> 1) & 3; u32 const bsize = bh >> 3;
+                    ZfBlock const bh = zf_block(srcA + pos);
+                    last = bh.last; u32 const btype = bh.type, bsize = bh.size;
                     pos += 3;
                     if (btype == 3) { go = false; break; }
                     if (btype == 0) { if (pos + bsize > srcSize) { go = false; break; } pos += bsize; if (last) covered = 0x80000000u; continue; }
                     if (btype == 1) { if (pos + 1 > srcSize) { go = false; break; } pos += 1; if (last) covered = 0x80000000u; continue; }
-                    if (pos + bsize > srcSize || bsize > 128u * 1024u || bsize < 2) { go = false; break; }
+                    if (pos + bsize > srcSize || bsize > ZF_BLOCK_MAX || bsize < 2) { go = false; break; }
                     const u8* const bp = srcA + pos; u32 const bend = bsize;
-                    u32 const lh0 = bp[0]; u32 const ltype = lh0 & 3, sf = (lh0 >> 2) & 3;
+                    ZfLiterals const lh = zf_literals(bp, bend);
+                    u32 const ltype = lh.type, lhSize = lh.header, regen = lh.regen, comp = lh.comp, nstreams = lh.streams;
                     KPreLit r; r.off = litUsed; r.regen = 0; r.ok = 0; r.pad = 0;
-                    if (ltype < 2) { a.rec[(size_t)fa * a.blk_cap + nb++] = r; pos += bsize; if (last) covered = 0x80000000u; continue; }      // raw / RLE literals: nothing to decode
-                    if (bend < 5) { go = false; break; }
-                    u32 const w = kx_ld32(bp); u32 lhSize, regen, comp, nstreams;
-                    if (sf < 2) { lhSize = 3; regen = (w >> 4) & 0x3FF; comp = (w >> 14) & 0x3FF; nstreams = sf ? 4 : 1; }
-                    else if (sf == 2) { lhSize = 4; regen = (w >> 4) & 0x3FFF; comp = w >> 18; nstreams = 4; }
-                    else { lhSize = 5; regen = (w >> 4) & 0x3FFFF; comp = (w >> 22) + ((u32)bp[4] << 10); nstreams = 4; }
-                    if (regen > 128u * 1024u || lhSize + comp > bend || comp == 0 || litUsed + regen > a.lit_cap) { go = false; break; }
+                    if (ltype < 2) { a.rec[(size_t)fa * a.blk_cap + nb++] = r; pos += bsize; if (last) covered = 0x80000000u; continue; }      // raw / RLE literals: nothing to decode, whatever their size
+                    if (!lh.fits) { go = false; break; }
+                    if (regen > ZF_BLOCK_MAX || lhSize + comp > bend || comp == 0 || litUsed + regen > a.lit_cap) { go = false; break; }
                     if (ltype == 3 && !hufValid) { go = false; break; }
                     // (a tree-less block: the table of the previous Huffman block is still in this frame's slice of the LDS)
                     if (ltype == 2) { L.treeOff = pos + lhSize; L.treeLen = comp < (u32)KXL_TREE ? comp : (u32)KXL_TREE; }
