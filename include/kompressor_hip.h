@@ -472,6 +472,76 @@ KMP_API int kmp_compact_batch(kmp_batch_ctx* ctx, const void* d_src, const uint6
                               const uint32_t* d_len, uint32_t n, void* d_dst, uint64_t* d_out_off,
                               void* hip_stream);
 
+/* zstd's seekable container (contrib/seekable_format upstream; no reference counterpart: the reference compresses one slice per call):
+ * ONE large buffer cut into independent frames of frame_bytes each, compressed as a batch -- the fast path -- and followed by a seek
+ * table, one skippable frame that lists every frame's compressed size, decompressed size and, with KMP_SEEKABLE_CHECKSUMS, the low 32
+ * bits of XXH64 (seed 0) of its content.  Any zstd decoder decodes the container as an ordinary .zst (it skips the table); a seekable
+ * reader fetches a byte range by decoding only the frames that cover it.  All fields little-endian:
+ *   seek table = 5E 2A 4D 18 | Frame_Size u32 = n * entry_bytes + 9 | entries | Number_Of_Frames u32 | Descriptor u8 | B1 EA 92 8F
+ *   entry      = Compressed_Size u32 | Decompressed_Size u32 | [Checksum u32]      Descriptor: bit 7 checksums, bits 6..2 must be 0
+ * The frames are bit for bit those kmp_zstd_compress_batch_level writes for the chunks (libzstd 1.5.7's), so the whole container is
+ * determined byte for byte by (input, frame_bytes, level, flags). */
+#define KMP_SEEKABLE_CHECKSUMS 1u
+/* room a container of src_size bytes needs: kmp_zstd_compress_bound of every chunk, plus the table (0: frame_bytes outside 1 .. 131 072) */
+KMP_API size_t kmp_zstd_seekable_bound(size_t src_size, uint32_t frame_bytes, uint32_t flags);
+/* device scratch (8-byte aligned) the compress call wants from its caller: the frames at bound-sized strides before they are packed,
+ * and the chunks' offset, length and checksum arrays.  The context allocates nothing for this feature: kmp_batch_memory answers the
+ * same before and after (a level's own first-use workspace, as kmp_zstd_compress_batch_level documents it for levels 4 .. 8, is that call's). */
+KMP_API size_t kmp_zstd_seekable_scratch(size_t src_size, uint32_t frame_bytes);
+/* d_src[0 .. src_size) -> the container at d_dst (dst_cap >= kmp_zstd_seekable_bound, else KMP_ERR_CAPACITY).  Asynchronous on
+ * hip_stream, no host wait: plan, the batch at `level`, XXH64 of every chunk (with checksums), kmp_compact_batch's packing, the table.
+ * frame_bytes: 1 .. 131 072 (else KMP_ERR_ARG) and at most the context's max_slice_bytes; the chunks, ceil(src_size / frame_bytes), at
+ * most its max_slices (else KMP_ERR_CAPACITY: rounds over a larger buffer are not served).  level: -131072 .. 8 (0 = 3), the levels
+ * kmp_zstd_compress_batch_level serves at every size up to 128 KiB; 9 and 10 are KMP_ERR_ARG (a short last chunk would be refused).
+ * d_result (device, 8-byte aligned): [0] = the container's size, or 0 when a chunk got no frame; [1] = the context's KMP_STATUS_* bits as
+ * they stand.  An empty input gives the 17 bytes of a table without entries. */
+KMP_API int kmp_zstd_seekable_compress(kmp_batch_ctx* ctx, const void* d_src, size_t src_size, uint32_t frame_bytes, int level, uint32_t flags,
+                                       void* d_dst, size_t dst_cap, void* d_scratch, size_t scratch_bytes, uint64_t* d_result /* [2] */,
+                                       void* hip_stream);
+/* What a container's table says.  status is libzstd's number: 0 good; 10 ("Unknown frame descriptor") a magic is missing or the blob
+ * is shorter than 17 bytes; 20 ("Data corruption detected") a reserved descriptor bit, a table larger than the blob or with more than
+ * 2^27 entries, a Frame_Size that disagrees, an entry above 1 GiB of content, or compressed sizes that do not sum to the table's
+ * offset.  With a status every other field is 0. */
+typedef struct {
+    uint64_t content;         /* decompressed bytes of the whole container */
+    uint64_t table_off;       /* where the frames end and the table begins */
+    uint32_t frames;          /* entries (an entry of decompressed size 0 may stand for a skippable frame inside the file) */
+    uint32_t max_frame;       /* the largest decompressed size of an entry: what a context must hold to read it */
+    uint32_t max_compressed;  /* the largest compressed size */
+    uint32_t flags;           /* KMP_SEEKABLE_CHECKSUMS */
+    uint32_t status;
+    uint32_t reserved;
+} kmp_seekable_stat;          /* 40 bytes */
+typedef struct kmp_seekable kmp_seekable;
+/* Validates the table of d_blob[0 .. blob_size) (device memory) on the device, then makes the ONE host wait of this feature: it reads
+ * the answer and the table back (12 bytes per frame with checksums, 8 without; a table beyond 256 KiB takes a second copy) and keeps the
+ * prefix sums of both sizes in the handle, on the host and -- as the arrays kmp_zstd_decompress_batch takes -- on the device (28 bytes per
+ * frame, owned by the handle).  A damaged table still gives a handle (KMP_OK): stat tells, and reads are refused.  A handle serves one
+ * stream at a time and must be closed before its context is destroyed. */
+KMP_API int kmp_zstd_seekable_open(kmp_batch_ctx* ctx, const void* d_blob, size_t blob_size, kmp_seekable** out, void* hip_stream);
+KMP_API void kmp_zstd_seekable_close(kmp_seekable* h);
+KMP_API int kmp_zstd_seekable_stat(const kmp_seekable* h, kmp_seekable_stat* stat);
+/* The same validation of a blob in HOST memory: the same code compiled for the host, no GPU touched, no context needed.  frame_off /
+ * content_off (each may be NULL): the prefix sums of the compressed / decompressed sizes, frames + 1 entries each, written when the
+ * status is 0 and prefix_cap >= frames + 1. */
+KMP_API int kmp_zstd_seekable_index_host(const void* h_blob, size_t blob_size, kmp_seekable_stat* stat,
+                                         uint64_t* frame_off, uint64_t* content_off, size_t prefix_cap);
+/* bytes a read of [lo, hi) writes: the covering frames whole (hi is cut at the content's end; 0 for an empty range or one past the end) */
+KMP_API size_t kmp_zstd_seekable_read_bound(const kmp_seekable* h, uint64_t lo, uint64_t hi);
+/* ... and how many frames cover it (0 for such a range): the statuses a read writes; *first (may be NULL) = the first one's index */
+KMP_API uint32_t kmp_zstd_seekable_read_frames(const kmp_seekable* h, uint64_t lo, uint64_t hi, uint32_t* first);
+/* Decodes the frames that cover [lo, hi), whole and back to back, into d_dst (dst_cap >= kmp_zstd_seekable_read_bound, else
+ * KMP_ERR_CAPACITY) with kmp_zstd_decompress_batch on the handle's context; *skip = lo minus the first covering frame's start, so the
+ * bytes asked for are d_dst[*skip .. *skip + hi - lo).  The covering frames come from the handle's host index: nothing is read back and
+ * the call is asynchronous.  More covering frames than the context's max_slices go through in rounds.  d_status (device, one uint32 per
+ * covering frame: kmp_zstd_seekable_read_frames says how many) receives 0 or libzstd's error code.  verify != 0 on a
+ * container with checksums: every decoded frame's XXH64 is compared with its entry on the device; a mismatch makes that frame's status
+ * 22 ("Restored data doesn't match checksum"), a decoded size other than the entry's 20.  d_blob: the container the handle was opened
+ * over.  An empty range or one past the end is KMP_OK with nothing written; a handle whose status is not 0 is KMP_ERR_ARG.  Frames
+ * larger than the context's max_slice_bytes (foreign containers) are decoded as far as kmp_zstd_decompress_batch decodes them. */
+KMP_API int kmp_zstd_seekable_read(kmp_seekable* h, const void* d_blob, uint64_t lo, uint64_t hi, int verify, void* d_dst, size_t dst_cap,
+                                   uint64_t* skip, uint32_t* d_status, void* hip_stream);
+
 /* Per-kernel device time of the last batch call, measured with HIP events on the
  * launch stream (0 = off, 1 = on).  kmp_batch_last_kernel_ms synchronises. */
 KMP_API int kmp_batch_set_profiling(kmp_batch_ctx* ctx, int on);

@@ -14,7 +14,7 @@ def __getattr__(name):
     if name in ("ZlibCompressor", "ZlibDecompressor", "ZlibFormat"):
         from . import zlib
         return getattr(zlib, name)
-    if name in ("ZstdBatch", "compress_bound"):
+    if name in ("ZstdBatch", "SeekableReader", "compress_bound"):
         from . import batch
         return getattr(batch, name)
     raise AttributeError(name)

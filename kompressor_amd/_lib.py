@@ -64,6 +64,16 @@ SIGNATURES = [
     ("kmp_zlib_decompress_stream", _c.c_int,
      [_P, _P, _c.c_size_t, _c.POINTER(_c.c_size_t), _P, _c.c_size_t, _c.POINTER(_c.c_size_t), _c.c_int]),
     ("kmp_compact_batch", _c.c_int, [_P, _P, _P, _P, _c.c_uint32, _P, _P, _P]),
+    ("kmp_zstd_seekable_bound", _c.c_size_t, [_c.c_size_t, _c.c_uint32, _c.c_uint32]),
+    ("kmp_zstd_seekable_scratch", _c.c_size_t, [_c.c_size_t, _c.c_uint32]),
+    ("kmp_zstd_seekable_compress", _c.c_int, [_P, _P, _c.c_size_t, _c.c_uint32, _c.c_int, _c.c_uint32, _P, _c.c_size_t, _P, _c.c_size_t, _P, _P]),
+    ("kmp_zstd_seekable_open", _c.c_int, [_P, _P, _c.c_size_t, _c.POINTER(_P), _P]),
+    ("kmp_zstd_seekable_close", None, [_P]),
+    ("kmp_zstd_seekable_stat", _c.c_int, [_P, _P]),
+    ("kmp_zstd_seekable_index_host", _c.c_int, [_P, _c.c_size_t, _P, _P, _P, _c.c_size_t]),
+    ("kmp_zstd_seekable_read_bound", _c.c_size_t, [_P, _c.c_uint64, _c.c_uint64]),
+    ("kmp_zstd_seekable_read_frames", _c.c_uint32, [_P, _c.c_uint64, _c.c_uint64, _c.POINTER(_c.c_uint32)]),
+    ("kmp_zstd_seekable_read", _c.c_int, [_P, _P, _c.c_uint64, _c.c_uint64, _c.c_int, _P, _c.c_size_t, _c.POINTER(_c.c_uint64), _P, _P]),
     ("kmp_batch_set_profiling", _c.c_int, [_P, _c.c_int]),
     ("kmp_batch_last_kernel_ms", _c.c_int, [_P, _c.c_int, _c.POINTER(_c.c_float)]),
     ("kmp_batch_last_chunks", _c.c_int, [_P]),
@@ -86,6 +96,11 @@ ABL_LIB_PATH = os.path.join(HERE, "libkompressor_hip_abl.so")    # the same sour
 
 class BatchOptions(_c.Structure):          # kmp_batch_options
     _fields_ = [("struct_bytes", _c.c_uint32), ("team_lanes", _c.c_int), ("table_span_gib", _c.c_int), ("table_retry", _c.c_int)]
+
+
+class SeekableStat(_c.Structure):         # kmp_seekable_stat
+    _fields_ = [("content", _c.c_uint64), ("table_off", _c.c_uint64), ("frames", _c.c_uint32), ("max_frame", _c.c_uint32),
+                ("max_compressed", _c.c_uint32), ("flags", _c.c_uint32), ("status", _c.c_uint32), ("reserved", _c.c_uint32)]
 
 
 class BatchMemoryInfo(_c.Structure):       # kmp_batch_memory_info

@@ -115,6 +115,71 @@ def host_engines_release(device=-1):
         raise RuntimeError(f"kmp_host_engines_release failed ({rc}): {_lib.last_error()}")
 
 
+class SeekableReader:
+    """A seekable zstd container in device memory, opened by ZstdBatch.open_seekable (kmp_zstd_seekable_open: the table is validated on
+    the device and read back once).  frames / content_size / checksums / max_frame are the table's; status is libzstd's number for a
+    table that was rejected (10 or 20: then every read raises)."""
+
+    def __init__(self, batch, blob):
+        self.batch, self.blob = batch, blob
+        h = ctypes.c_void_p()
+        rc = batch.lib.kmp_zstd_seekable_open(batch._h, _ptr(blob), blob.numel(), ctypes.byref(h), batch._stream())
+        if rc != 0:
+            raise RuntimeError(f"kmp_zstd_seekable_open failed ({rc}): {batch._err()}")
+        self._h = h
+        st = _lib.SeekableStat()
+        batch.lib.kmp_zstd_seekable_stat(h, ctypes.byref(st))
+        self.status, self.frames, self.content_size, self.max_frame = int(st.status), int(st.frames), int(st.content), int(st.max_frame)
+        self.checksums = bool(st.flags & 1)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self.batch.lib.kmp_zstd_seekable_close(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def read_frames(self, lo, hi, verify=True):
+        """kmp_zstd_seekable_read, queued with no host wait: the frames covering [lo, hi) decoded whole into one buffer.
+        -> (dst, skip, status): the bytes asked for are dst[skip : skip + hi - lo]; status: int32 device tensor, one per covering frame
+        (0, libzstd's error code, 22 for a checksum that does not match under verify)."""
+        lib, b = self.batch.lib, self.batch
+        if self.status:
+            raise RuntimeError(f"the container's seek table was rejected (status {self.status})")
+        need = lib.kmp_zstd_seekable_read_bound(self._h, lo, hi)
+        m = lib.kmp_zstd_seekable_read_frames(self._h, lo, hi, None)
+        dst = torch.empty(need + 64, dtype=torch.uint8, device=b.device)
+        status = torch.zeros(max(m, 1), dtype=torch.int32, device=b.device)
+        skip = ctypes.c_uint64()
+        rc = lib.kmp_zstd_seekable_read(self._h, _ptr(self.blob), lo, hi, 1 if verify else 0, _ptr(dst), need, ctypes.byref(skip), _ptr(status), b._stream())
+        if rc != 0:
+            raise RuntimeError(f"kmp_zstd_seekable_read failed ({rc}): {b._err()}")
+        return dst, int(skip.value), status[:m]
+
+    def read(self, lo, hi, verify=True):
+        """Bytes [lo, hi) of the content (hi is cut at the content's end): a uint8 device tensor view of exactly that many bytes.
+        verify: on a container with checksums, compare every decoded frame's XXH64 with its entry.  Reads the frames' statuses back
+        (a host wait) and raises on a nonzero one."""
+        if self.status:
+            raise RuntimeError(f"the container's seek table was rejected (status {self.status})")
+        hi = min(hi, self.content_size)
+        if lo >= hi:
+            return torch.empty(0, dtype=torch.uint8, device=self.batch.device)
+        dst, skip, status = self.read_frames(lo, hi, verify)
+        bad = torch.nonzero(status).flatten().tolist()
+        if bad:
+            codes = status.tolist()
+            raise RuntimeError(f"seekable read [{lo}, {hi}): frame status " + ", ".join(f"+{i}: {codes[i]}" for i in bad[:8]))
+        return dst[skip:skip + hi - lo]
+
+    def read_all(self, verify=True):
+        return self.read(0, self.content_size, verify)
+
+
 class ZstdBatch:
     """Owns the device workspace for batches of up to `max_slices` slices of up to
     `max_slice_bytes` bytes (<= 128 KiB) on one GPU."""
@@ -245,6 +310,33 @@ class ZstdBatch:
         if check:
             self._check("kmp_zstd_compress_batch")
         return dst, out_off, out_len
+
+    def compress_seekable(self, src, frame_bytes=65536, level=3, checksums=True):
+        """One buffer (uint8 device tensor) -> a seekable zstd container (kmp_zstd_seekable_compress): independent frames of frame_bytes
+        (1 .. 131 072, at most the context's max_slice_bytes; at most max_slices of them) at `level` (-131072 .. 8), then the seek table
+        with, by default, each frame's XXH64 checksum.  Any zstd decoder decodes the result; open_seekable reads byte ranges of it.
+        Returns a uint8 device tensor trimmed to the container: the one host wait is the .item() that reads its size to trim it."""
+        n = src.numel()
+        flags = 1 if checksums else 0
+        cap = self.lib.kmp_zstd_seekable_bound(n, frame_bytes, flags)
+        need = self.lib.kmp_zstd_seekable_scratch(n, frame_bytes)
+        if cap == 0:
+            raise ValueError("frame_bytes must be 1 .. 131072")
+        dst = torch.empty(cap + 64, dtype=torch.uint8, device=self.device)
+        scratch = torch.empty((need + 7) // 8, dtype=torch.int64, device=self.device)
+        result = torch.zeros(2, dtype=torch.int64, device=self.device)
+        rc = self.lib.kmp_zstd_seekable_compress(self._h, _ptr(src) if n else None, n, frame_bytes, level, flags, _ptr(dst), cap, _ptr(scratch), need,
+                                                 _ptr(result), self._stream())
+        if rc != 0:
+            raise RuntimeError(f"kmp_zstd_seekable_compress failed ({rc}): {self._err()}")
+        size = int(result[0].item())
+        if size == 0:
+            raise RuntimeError(f"kmp_zstd_seekable_compress: a chunk got no frame (status bits {int(result[1].item()):#x})")
+        return dst[:size]
+
+    def open_seekable(self, blob):
+        """A SeekableReader over a container in device memory (uint8 tensor; it must stay alive while the reader is used)."""
+        return SeekableReader(self, blob)
 
     def piece_range(self, n, pieces, piece):
         """(first, count) of part `piece` of an n-slice batch cut into `pieces` (kmp_batch_piece_range)."""

@@ -287,26 +287,43 @@ KX_DEV u64 kxxh_round(u64 acc, u64 in)
     acc += in * 14029467366897019727ULL; acc = (acc << 31) | (acc >> 33); return acc * 11400714785074694791ULL;
 }
 KX_DEV u64 kxxh_merge(u64 acc, u64 v) { v = kxxh_round(0, v); acc ^= v; return acc * 11400714785074694791ULL + 9650029242287828579ULL; }
-KX_DEV u64 kxxh64(const u8* p, u32 len)
+// XXH64 (seed 0) in the three parts a caller with its own stripe loop needs too (zstd_seekable.h spreads the four accumulators over
+// four lanes): the start values, the four accumulators folded into one, and everything behind the last whole stripe of 32 bytes
+KX_DEV u64 kxxh64_start(u32 j)
+{
+    const u64 P1 = 11400714785074694791ULL, P2 = 14029467366897019727ULL;
+    return j == 0 ? P1 + P2 : j == 1 ? P2 : j == 2 ? 0 : 0 - P1;
+}
+KX_DEV u64 kxxh64_fold(u64 v1, u64 v2, u64 v3, u64 v4)
+{
+    u64 h = ((v1 << 1) | (v1 >> 63)) + ((v2 << 7) | (v2 >> 57)) + ((v3 << 12) | (v3 >> 52)) + ((v4 << 18) | (v4 >> 46));
+    h = kxxh_merge(h, v1); h = kxxh_merge(h, v2); h = kxxh_merge(h, v3); h = kxxh_merge(h, v4);
+    return h;
+}
+// h: the folded accumulators, or P5 for an input below 32 bytes; i: the bytes the stripes took
+KX_DEV u64 kxxh64_finish(u64 h, const u8* p, u32 i, u32 len)
 {
     const u64 P1 = 11400714785074694791ULL, P2 = 14029467366897019727ULL, P3 = 1609587929392839161ULL,
               P4 = 9650029242287828579ULL, P5 = 2870177450012600261ULL;
-    u64 h; u32 i = 0;
-    if (len >= 32) {
-        u64 v1 = P1 + P2, v2 = P2, v3 = 0, v4 = 0 - P1;
-        for (; i + 32 <= len; i += 32) {
-            v1 = kxxh_round(v1, kx_ld64(p + i)); v2 = kxxh_round(v2, kx_ld64(p + i + 8));
-            v3 = kxxh_round(v3, kx_ld64(p + i + 16)); v4 = kxxh_round(v4, kx_ld64(p + i + 24));
-        }
-        h = ((v1 << 1) | (v1 >> 63)) + ((v2 << 7) | (v2 >> 57)) + ((v3 << 12) | (v3 >> 52)) + ((v4 << 18) | (v4 >> 46));
-        h = kxxh_merge(h, v1); h = kxxh_merge(h, v2); h = kxxh_merge(h, v3); h = kxxh_merge(h, v4);
-    } else h = P5;
     h += len;
     for (; i + 8 <= len; i += 8) { h ^= kxxh_round(0, kx_ld64(p + i)); h = ((h << 27) | (h >> 37)) * P1 + P4; }
     if (i + 4 <= len) { h ^= (u64)kx_ld32(p + i) * P1; h = ((h << 23) | (h >> 41)) * P2 + P3; i += 4; }
     for (; i < len; i++) { h ^= p[i] * P5; h = ((h << 11) | (h >> 53)) * P1; }
     h ^= h >> 33; h *= P2; h ^= h >> 29; h *= P3; h ^= h >> 32;
     return h;
+}
+KX_DEV u64 kxxh64(const u8* p, u32 len)
+{
+    u64 h = 2870177450012600261ULL; u32 i = 0;
+    if (len >= 32) {
+        u64 v1 = kxxh64_start(0), v2 = kxxh64_start(1), v3 = kxxh64_start(2), v4 = kxxh64_start(3);
+        for (; i + 32 <= len; i += 32) {
+            v1 = kxxh_round(v1, kx_ld64(p + i)); v2 = kxxh_round(v2, kx_ld64(p + i + 8));
+            v3 = kxxh_round(v3, kx_ld64(p + i + 16)); v4 = kxxh_round(v4, kx_ld64(p + i + 24));
+        }
+        h = kxxh64_fold(v1, v2, v3, v4);
+    }
+    return kxxh64_finish(h, p, i, len);
 }
 
 KX_DEV u32 kx_ll_base(u32 c)
