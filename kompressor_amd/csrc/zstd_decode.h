@@ -494,7 +494,7 @@ KX_DEV KxdExecResult kxd_exec_window(const u8* dict, u32 dict_size, u32 flags, c
             if (litUsed + llE > regen) KXD_EXEC_FAIL(KZE_CORRUPT)
             if ((u64)op + llE + mlE > cap) KXD_EXEC_FAIL(KZE_DSTSMALL)
             u32 const dE = op + llE;
-            if (offE > dE - fbase + dict_size) KXD_EXEC_FAIL(KZE_CORRUPT)
+            if (offE - 1u >= dE - fbase + dict_size) KXD_EXEC_FAIL(KZE_CORRUPT)              // (an offset of 0 included)
             if (!(flags & 4u)) {
                 kxd_wave_copy(dst + op, litPtr + litUsed, llE, lane);
                 kx_lockstep();
@@ -531,7 +531,7 @@ KX_DEV KxdExecResult kxd_exec_window(const u8* dict, u32 dict_size, u32 flags, c
         u32 const dlit = op + (st - ll - ml);         // where they go
         u32 const dmat = dlit + ll;                   // where my match goes
         // a match may start inside the dictionary (the history before the frame's first byte)
-        if (kx_any(own && off > dmat - fbase + dict_size)) KXD_EXEC_FAIL(KZE_CORRUPT)
+        if (kx_any(own && off - 1u >= dmat - fbase + dict_size)) KXD_EXEC_FAIL(KZE_CORRUPT)      // (an offset of 0 included)
         if (!(flags & 4u)) {
             if ((op - winBase) + totOut > KXD_WIN) winBase = op;      // no room behind the history: start over
             // ---- everything that depends on nothing in this chunk, with every HBM load in flight at once ----
@@ -678,6 +678,9 @@ KX_DEV void zstd_decode_frame(const KDecodeArgs& a, KDecodeLds& lds, u32 f, int 
         checksum = fd.checksum;
         if (fd.reserved) err = KZE_FRAMEPARAM;
         if (!err && fd.header_size > srcSize - pos) err = KZE_SRCSIZE;
+        // the frame's block maximum, and what the blocks are refused for at the frame's end (below), wait in LDS: no register is kept
+        // for either while a block's sequences are executed
+        if (lane == 0) { lds.bc[8] = err ? ZF_BLOCK_MAX : zf_block_max(src + pos, fd); lds.bc[9] = 0; }
         pos += 5;
         if (!err && !fd.single) { if (zf_window(src[pos]).log > 31) err = KZE_WINDOW; pos++; }
         if (!err) {
@@ -782,6 +785,7 @@ KX_DEV void zstd_decode_frame(const KDecodeArgs& a, KDecodeLds& lds, u32 f, int 
             if (nstreams == 1) {
                 if (lane == 0 && !(a.flags & 1u)) ok = khuf_decode_stream(lds, hufLog, sp, ssize, lits, regen);
             } else {
+                if (regen < 6) { err = KZE_LITHDR; break; }              // libzstd: MIN_LITERALS_FOR_4_STREAMS, "literals_headerWrong"
                 if (ssize < 10) { err = KZE_CORRUPT; break; }
                 u32 const c0 = kx_ld16(sp), c1 = kx_ld16(sp + 2), c2 = kx_ld16(sp + 4);
                 if (6 + c0 + c1 + c2 > ssize) { err = KZE_CORRUPT; break; }
@@ -804,6 +808,14 @@ KX_DEV void zstd_decode_frame(const KDecodeArgs& a, KDecodeLds& lds, u32 f, int 
         ZfSequences const sh = zf_sequences(bp, lpos, bend);
         if (!sh.have_count || (sh.count && (!sh.have_modes || (sh.modes & 3)))) { err = KZE_CORRUPT; break; }
         u32 const nbSeq = sh.count, modes = sh.modes; u32 spos = sh.next;
+        // Three things libzstd refuses a block for up front are answered at the frame's end here, in its order, so that a block
+        // refused for another reason keeps its code: a compressed block larger than the frame's block maximum ("Src size is
+        // incorrect"), literals larger than it, bytes behind a sequence count of 0.  The first block's answer is kept.
+        {
+            u32 const blockMax = lds.bc[8];
+            u32 const late = bsize > blockMax ? (u32)KZE_SRCSIZE : (regen > blockMax || (!nbSeq && spos != bend)) ? (u32)KZE_CORRUPT : 0u;
+            if (late && lane == 0 && !lds.bc[9]) lds.bc[9] = late;
+        }
         // this block's sequences may lie decoded in HBM already (k_zstd_seq_predecode)
         const u64* preSeq = nullptr; u32 preRep1 = 0, preRep2 = 0, preRep3 = 0;
         if (ord < npre) {
@@ -925,7 +937,7 @@ KX_DEV void zstd_decode_frame(const KDecodeArgs& a, KDecodeLds& lds, u32 f, int 
                         // repeat-offset rules
                         bool const isRep = ofv <= 3;
                         u32 const idx = ofv - 1 + (ll == 0);                       // meaningful when isRep
-                        u32 const rm1 = (rep1 - 1) ? rep1 - 1 : 1u;
+                        u32 const rm1 = rep1 - 1;                                  // (0 is no offset: refused where the match is placed, as libzstd 1.5.7 does)
                         u32 const roff = idx == 0 ? rep1 : idx == 1 ? rep2 : idx == 2 ? rep3 : rm1;
                         u32 const off = isRep ? roff : ofv - 3;
                         bool const sh2 = !isRep || idx >= 2, sh1 = !isRep || idx >= 1;
@@ -953,7 +965,7 @@ KX_DEV void zstd_decode_frame(const KDecodeArgs& a, KDecodeLds& lds, u32 f, int 
                 u32 const dlit = op + (st - ll - ml);         // where they go
                 u32 const dmat = dlit + ll;                   // where my match goes
                 // a match may start inside the dictionary (the history before the frame's first byte)
-                if (kx_any(own && off > dmat - fbase + a.dict_size)) { err = KZE_CORRUPT; break; }
+                if (kx_any(own && off - 1u >= dmat - fbase + a.dict_size)) { err = KZE_CORRUPT; break; }      // (an offset of 0 included)
                 // literals: short runs lane-serially (exact length), long runs by the whole wave
                 if (a.flags & 4u) { op += totOut; litUsed += totLit; kx_sync(); done += cnt; continue; }
                 if (own && ll <= 32) kxd_copy32(dst + dlit, litPtr + lp, ll);
@@ -1035,9 +1047,12 @@ KX_DEV void zstd_decode_frame(const KDecodeArgs& a, KDecodeLds& lds, u32 f, int 
         kx_sync();
     }
     kx_sync();
-    if (!err && hasContent && contentSize != op - fbase) err = KZE_CORRUPT;
+    u32 const late = lds.bc[9];
+    kx_sync();                                 // (the next frame's header writes the slot)
+    if (!err && hasContent && contentSize != op - fbase) err = KZE_CORRUPT;      // (before the blocks' late answer: a frame that was refused for its size keeps that code)
+    if (!err) err = late;
     if (!err && checksum) {
-        if (pos + 4 > srcSize) err = KZE_SRCSIZE;
+        if (pos + 4 > srcSize) err = KZE_CHECKSUM;               // (libzstd: a checksum word cut short is a wrong checksum)
         else {
             u32 bad = 0;
             if (lane == 0) bad = ((u32)kxxh64(dst + fbase, op - fbase) != kx_ld32(src + pos)) ? 1u : 0u;

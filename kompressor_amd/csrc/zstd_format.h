@@ -47,6 +47,13 @@ ZF_HD ZfWindow zf_window(uint32_t window_byte)
 }
 // the content size field of fcs_bytes = 1, 2, 4, 8 bytes (the 2-byte form counts from 256)
 ZF_HD uint64_t zf_content_size(const uint8_t* p, uint32_t fcs_bytes) { return zf_le(p, fcs_bytes) + (fcs_bytes == 2u ? 256u : 0u); }
+// the most bytes a compressed block of the frame may take: min(window size, 128 KiB); a single-segment frame's window is its content
+// size.  hdr: the frame's magic; d.header_size bytes lie there.
+ZF_HD uint32_t zf_block_max(const uint8_t* hdr, ZfDescriptor d)
+{
+    uint64_t const w = d.single ? zf_content_size(hdr + 5 + d.did_bytes, d.fcs_bytes) : zf_window(hdr[5]).size;
+    return w < ZF_BLOCK_MAX ? (uint32_t)w : ZF_BLOCK_MAX;
+}
 
 // ---- block header: 3 bytes.  type: 0 raw, 1 RLE (size = the run; one byte follows), 2 compressed, 3 reserved ----
 struct ZfBlock { uint32_t last, type, size; };

@@ -330,7 +330,7 @@ KX_DEV void zstd_seq_predecode_body(const KPreArgs& a)
             // repeat-offset rules
             bool const isRep = ofv <= 3;
             u32 const idx = ofv - 1 + (ll == 0);
-            u32 const rm1 = (rep1 - 1) ? rep1 - 1 : 1u;
+            u32 const rm1 = rep1 - 1;                                      // (0 is no offset: k_zstd_decode refuses the sequence where it places the match)
             u32 const roff = idx == 0 ? rep1 : idx == 1 ? rep2 : idx == 2 ? rep3 : rm1;
             u32 const off = isRep ? roff : ofv - 3;
             bool const sh2 = !isRep || idx >= 2, sh1 = !isRep || idx >= 1;
@@ -555,6 +555,7 @@ KX_DEV void zstd_lit_predecode_body(const KLitArgs& a)
                     if (!lh.fits) { go = false; break; }
                     if (regen > ZF_BLOCK_MAX || lhSize + comp > bend || comp == 0 || litUsed + regen > a.lit_cap) { go = false; break; }
                     if (ltype == 3 && !hufValid) { go = false; break; }
+                    if (nstreams == 4 && regen < 6) { go = false; break; }       // "literals_headerWrong": k_zstd_decode says so
                     // (a tree-less block: the table of the previous Huffman block is still in this frame's slice of the LDS)
                     if (ltype == 2) { L.treeOff = pos + lhSize; L.treeLen = comp < (u32)KXL_TREE ? comp : (u32)KXL_TREE; }
                     regenA = regen; lhSizeA = lhSize; compA = comp; nstreamsA = nstreams; ltypeA = ltype; bposA = pos;
