@@ -546,12 +546,19 @@ KMP_API int kmp_zstd_seekable_read(kmp_seekable* h, const void* d_blob, uint64_t
 /* Per-kernel device time of the last batch call, measured with HIP events on the
  * launch stream (0 = off, 1 = on).  kmp_batch_last_kernel_ms synchronises. */
 KMP_API int kmp_batch_set_profiling(kmp_batch_ctx* ctx, int on);
-/* which: 0 = zstd_match, 1 = zstd_entropy (mean over the launches of the last compress batch), 2 = zstd_decode */
+/* which: 0 = zstd_match, 1 = zstd_entropy (mean over the launches of the last compress batch), 2 = zstd_decode.
+ * A large level-3 batch is entropy-coded by sweeps that run beside the parse and a final one behind it (kmp_batch_last_sweeps):
+ * for such a batch 1 is the final sweep alone -- the entropy time that is still exposed, not the coding time of the whole batch. */
 KMP_API int kmp_batch_last_kernel_ms(kmp_batch_ctx* ctx, int which, float* ms);
 /* kmp_zstd_compress_batch cuts a large batch into chunks so that k_zstd_entropy of one chunk runs beside
  * k_zstd_match of the next (second HIP stream inside the context; the caller's stream still sees the whole
  * batch finished).  Returns how many launches of each kernel the last batch used. */
 KMP_API int kmp_batch_last_chunks(kmp_batch_ctx* ctx);
+/* Entropy sweeps of the last level-3 batch: k_zstd_entropy launches that code the slices the parse has finished while it is
+ * still running, and a final one behind it.  Returns how many were launched, the final one included (0: the batch was coded by
+ * plain launches; -1: error), and with profiling on writes the slices each coded into coded[0 .. min(cap, return)), in launch
+ * order.  Synchronises with the batch. */
+KMP_API int kmp_batch_last_sweeps(kmp_batch_ctx* ctx, uint32_t* coded, uint32_t cap);
 /* A context for slices above 128 KiB compresses block by block (libzstd decides each block's size from the bytes
  * produced so far): block rounds of the last batch. */
 KMP_API int kmp_batch_last_rounds(kmp_batch_ctx* ctx);

@@ -77,6 +77,7 @@ SIGNATURES = [
     ("kmp_batch_set_profiling", _c.c_int, [_P, _c.c_int]),
     ("kmp_batch_last_kernel_ms", _c.c_int, [_P, _c.c_int, _c.POINTER(_c.c_float)]),
     ("kmp_batch_last_chunks", _c.c_int, [_P]),
+    ("kmp_batch_last_sweeps", _c.c_int, [_P, _c.POINTER(_c.c_uint32), _c.c_uint32]),
     ("kmp_batch_last_rounds", _c.c_int, [_P]),
     ("kmp_zstd_compress_host_batch", _c.c_int, [_c.c_int, _c.c_int, _P, _P, _P, _c.c_uint32, _P, _P, _P, _P]),
     ("kmp_zstd_decompress_host_batch", _c.c_int, [_c.c_int, _P, _P, _P, _c.c_uint32, _P, _P, _P, _P, _P]),

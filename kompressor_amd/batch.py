@@ -256,6 +256,15 @@ class ZstdBatch:
         """Launches of each zstd compress kernel in the last batch."""
         return int(self.lib.kmp_batch_last_chunks(self._h))
 
+    def last_sweeps(self):
+        """Slices coded by each entropy sweep of the last level-3 batch, in launch order, the final sweep last (counted with
+        profiling on, else zeros); [] when the batch was coded by plain launches."""
+        buf = (ctypes.c_uint32 * 32)()
+        k = int(self.lib.kmp_batch_last_sweeps(self._h, buf, 32))
+        if k < 0:
+            raise RuntimeError(self._err())
+        return [int(buf[i]) for i in range(min(k, 32))]
+
     def _check(self, what):
         """check=True of compress / deflate: wait for the batch and raise on a status bit (a slice longer than the context
         holds, a parser guard) instead of handing back frames of length 0."""

@@ -19,11 +19,21 @@
 #include <thread>
 #include <vector>
 
+// entropy sweeps: K of a context unless KMP_ENTROPY_SWEEPS says otherwise (the ablation build), and the words in front of done[] in
+// kmp_batch_ctx.sweep_rec: [0] the count the stream waits read, [1 + j] slices coded by sweep j.  K = 8: 201.9 ms a step against
+// 202.3 at K = 4, 203.1 at K = 16 and 205.6 without sweeps (65 536 x 64 KiB, profiles/overlap_entropy.txt)
+enum { KMP_SWEEPS_DEFAULT = 8, KMP_SWEEP_HEAD = 32 };
+static_assert(KMP_SWEEP_HEAD > KX_MAX_SWEEPS + 1, "a counter per sweep, the final one included");
+
 // --------------------------------------------------------------------------
 // kernels (one 64-lane wave per workgroup everywhere)
 // --------------------------------------------------------------------------
 template <int G>
 __global__ __launch_bounds__(64) void k_zstd_match(KMatchArgs a) { zstd_match_body<G>(a); }
+// Team width 4, the level-3 default: five waves' worth of registers per SIMD (<= 96 VGPRs each).  The launch itself puts four
+// parse waves on a SIMD, so one wave of k_zstd_entropy (128 VGPRs) fits beside them: the entropy sweeps (zstd_compress_dfast)
+template <>
+__global__ __launch_bounds__(64, 5) void k_zstd_match<4>(KMatchArgs a) { zstd_match_body<4>(a); }
 #ifdef KMP_ABLATIONS
 // the same parse as a split-phase stage machine (zstd_match2.h): one memory round trip per outer iteration
 template <int G, int R>
@@ -535,6 +545,14 @@ static int batch_create_body(kmp_batch_ctx* c, int device, uint32_t max_slices, 
     // (k_zstd_lit_predecode, one lane per stream)
     c->knob.decode_pre = KMP_KNOB("KMP_DECODE_PRE", 3); c->knob.decode_sort = KMP_KNOB("KMP_DECODE_SORT", 1); c->knob.decode_pieces = KMP_KNOB("KMP_DECODE_PIECES", 1); c->knob.decode_stage_slices = env_u32("KMP_DECODE_STAGE_SLICES", 0); c->knob.inflate_pre = KMP_KNOB("KMP_INFLATE_PRE", 1); c->knob.inflate_pieces = KMP_KNOB("KMP_INFLATE_PIECES", 1); c->knob.autotune = KMP_KNOB("KMP_ZSTD_AUTOTUNE", 0);      // opt-in: one launch or two chunks, tried once each (two blocking event reads on the 2nd / 3rd batch)
     c->knob.fuse = KMP_KNOB("KMP_FUSE", 0);                             // 1: k_zstd_l3_fused (the entropy stage inside the parse kernel's waves)
+    // entropy sweeps beside the level-3 parse: K (0: off) and the smallest batch that takes the path
+    c->knob.sweeps = KMP_KNOB("KMP_ENTROPY_SWEEPS", KMP_SWEEPS_DEFAULT); if (c->knob.sweeps > KX_MAX_SWEEPS) c->knob.sweeps = KX_MAX_SWEEPS;
+    c->knob.sweep_min = KMP_KNOB("KMP_ENTROPY_SWEEP_MIN", 16384);
+    { int v = 0; if (hipDeviceGetAttribute(&v, hipDeviceAttributeCanUseStreamWaitValue, device) == hipSuccess) c->can_wait_value = v; else (void)hipGetLastError(); }
+    if (!c->big && c->knob.sweeps && c->can_wait_value) {
+        KMP_TRY(c->sweep_rec.alloc((KMP_SWEEP_HEAD + 2 * ns) * sizeof(u32), "hipMalloc(sweep records)"));
+        KMP_TRY(c->ev_fork.create(hipEventDisableTiming));
+    }
     c->knob.match_v2 = KMP_KNOB("KMP_MATCH_V2", 0);                     // 0: zstd_match.h (the default: 4 % faster, both sit on the same memory floor); 1: zstd_match2.h; 2: with a 512-byte window at team width 4
     HIP_TRY(hipStreamSynchronize(c->st2));
     return KMP_OK;
@@ -558,7 +576,7 @@ extern "C" int kmp_batch_memory(kmp_batch_ctx* c, kmp_batch_memory_info* info)
     m.arena = c->arena.bytes;
     if (c->arena) m.arena_used = (size_t)c->nteams * KX_TBL_ENTRIES * sizeof(u32) + ns * c->seq_cap * sizeof(KSeq) + ns * c->lit_cap + ns * sizeof(KSliceMeta) + ns * c->scratch_words * sizeof(u32);
     m.workspace = c->seqs_buf.bytes + c->lits_buf.bytes + c->meta_buf.bytes + c->scratch_buf.bytes + c->tables_buf.bytes
-                + c->team_epoch.bytes + c->counter.bytes + c->len_ok.bytes + c->d_status.bytes;
+                + c->team_epoch.bytes + c->counter.bytes + c->len_ok.bytes + c->d_status.bytes + c->sweep_rec.bytes;
     m.other_tables = part_bytes(c->flat) + part_bytes(c->t4) + part_bytes(c->chain_t4) + dict_bytes(c) + part_bytes(c->ddict) + part_bytes(c->lz) + part_bytes(c->lzb);
     m.block_chain = c->fstate.bytes + c->hufct.bytes + c->big_tables.bytes + c->remaining.bytes + c->big_counters.bytes;
     m.decode_staging = part_bytes(c->pre_seq) + part_bytes(c->pre_lit);
@@ -569,7 +587,8 @@ extern "C" int kmp_batch_memory(kmp_batch_ctx* c, kmp_batch_memory_info* info)
 }
 
 extern "C" int kmp_batch_set_profiling(kmp_batch_ctx* c, int on) { if (!c) return KMP_ERR_ARG; c->profiling = on; return KMP_OK; }
-// 0 / 1: mean duration of the k_zstd_match / k_zstd_entropy launches of the last timed level-3 batch; 2: decode; 3: DEFLATE
+// 0 / 1: mean duration of the k_zstd_match / k_zstd_entropy launches of the last timed level-3 batch; 2: decode; 3: DEFLATE.
+// A batch with entropy sweeps beside its parse: 1 is the final sweep alone, the entropy time the step still shows.
 extern "C" int kmp_batch_last_kernel_ms(kmp_batch_ctx* c, int which, float* ms)
 {
     int const timed = !c || !ms ? 0 : which == 0 || which == 1 ? c->zstd_timed : which == 2 ? c->decode_timed : which == 3 ? c->deflate_timed : 0;
@@ -606,6 +625,18 @@ extern "C" int kmp_debug_copy_meta(kmp_batch_ctx* c, void* h_dst, uint32_t n)
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(h_dst, c->meta, (size_t)n * sizeof(KSliceMeta), hipMemcpyDeviceToHost));
     return KMP_OK;
+}
+/* entropy sweeps of the last level-3 batch: how many were launched, the final one included (0: the batch took the plain path), and
+ * with profiling on the slices each of them coded, in launch order.  Waits for the batch. */
+extern "C" int kmp_batch_last_sweeps(kmp_batch_ctx* c, uint32_t* coded, uint32_t cap)
+{
+    if (!c || (cap && !coded)) { g_last_error = "kmp_batch_last_sweeps: null argument"; return -1; }
+    u32 const k = c->last_sweeps < cap ? c->last_sweeps : cap;
+    if (k) {
+        if (hipSetDevice(c->device) != hipSuccess || (c->have_done && hipEventSynchronize(c->ev_done) != hipSuccess)
+            || hipMemcpy(coded, c->sweep_rec + 1, k * sizeof(u32), hipMemcpyDeviceToHost) != hipSuccess) { (void)hip_fail(hipGetLastError(), "kmp_batch_last_sweeps"); return -1; }
+    }
+    return (int)c->last_sweeps;
 }
 /* launches of each zstd compress kernel in the last batch (the batch is cut into that many chunks) */
 extern "C" int kmp_batch_last_chunks(kmp_batch_ctx* c) { return c ? (int)c->last_chunks : 0; }
@@ -1177,6 +1208,11 @@ static int zstd_compress_dfast(kmp_batch_ctx* c, const void* d_src, const uint64
     // two chunks: the last entropy launch is the only one nothing runs beside, so the second chunk is the smaller one
     if (chunks == 2) { u32 const pm = c->knob.first_permille; if (pm >= 100 && pm <= 950) starts[1] = (u32)((u64)n * pm / 1000u) & ~63u; if (starts[1] == 0 || starts[1] >= n) starts[1] = per; }
     bool forked = false;
+    // Entropy sweeps beside the parse: level 3, one launch, team width 4 (the parse kernel that leaves a wave slot free) and a batch
+    // large enough to fill the device; neither of the ablation build's other forms of the step
+    bool const sweep = !l4 && chunks == 1 && G == 4 && c->sweep_rec && n >= c->knob.sweep_min && !c->knob.fuse && !c->knob.match_v2 && (match_flags & KXM_NO_LITS);
+    KSweepRecords const rec = { c->sweep_rec + KMP_SWEEP_HEAD, c->sweep_rec + KMP_SWEEP_HEAD + n, c->sweep_rec };
+    c->last_sweeps = 0;
     KBatchView const v = batch_view(c, d_src, d_in_off, n, d_dst, d_out_off, d_out_len);
     KTeamTables const tables = l4 ? kx_one_piece(c->t4->tables, c->t4->epochs, true) : team_tables(c);
     for (u32 ci = 0; ci < chunks; ci++) {
@@ -1184,6 +1220,12 @@ static int zstd_compress_dfast(kmp_batch_ctx* c, const void* d_src, const uint64
         if (m_n == 0) continue;
         KBatchView const cv = v.sub(first, m_n);
         KMatchArgs m = kx_match_args(cv, tables, c->counter + ci, match_flags);
+        if (sweep) {
+            // cleared per batch on the caller's stream; the second stream starts behind the clears, so no wait reads an old count
+            HIP_TRY(hipMemsetAsync(c->sweep_rec, 0, (KMP_SWEEP_HEAD + 2 * (size_t)n) * sizeof(u32), st));
+            HIP_TRY(hipEventRecord(c->ev_fork, st));
+            kx_match_records(m, rec);
+        }
         u32 max_blocks = (u32)((u64)c->match_blocks_l3 * (64u / (u32)c->G) / tpw);      // the context's team slots at this batch's width
         if (l4 && max_blocks > c->t4->teams / tpw) max_blocks = c->t4->teams / tpw;
         u32 blocks = (m_n + tpw - 1) / tpw; if (blocks > max_blocks) blocks = max_blocks;
@@ -1218,6 +1260,26 @@ static int zstd_compress_dfast(kmp_batch_ctx* c, const void* d_src, const uint64
         }
         HIP_TRY(hipEventRecord(c->match[ci].end, st));
         KEntropyArgs const e = kx_entropy_args(cv, c->knob.entropy_flags | kx_entropy_flags_dfast(m.flags, l4));
+        if (sweep) {
+            // Sweep j starts once the parse has counted T_j finished slices (hipStreamWaitValue32, queued behind the parse's launch,
+            // and the parse counts every slice: zstd_match.h KST_CLEANUP) and codes whatever is finished and uncoded by then, in the
+            // wave slot the parse leaves free on every SIMD.  No kernel waits for anything.  The final sweep runs on the caller's
+            // stream behind the parse and the other sweeps and codes the rest: the frames do not depend on what ran when.
+            u32 T[KX_MAX_SWEEPS]; u32 const nt = kx_sweep_thresholds(n, c->knob.sweeps, T);
+            HIP_TRY(hipStreamWaitEvent(c->st2, c->ev_fork, 0));
+            for (u32 j = 0; j < nt; j++) {
+                HIP_TRY(hipStreamWaitValue32(c->st2, rec.count, T[j], hipStreamWaitValueGte, 0xFFFFFFFFu));
+                hipLaunchKernelGGL(k_zstd_entropy, dim3(m_n), dim3(64), 0, c->st2, kx_entropy_sweep_args(e, rec, c->profiling ? c->sweep_rec + 1 + j : nullptr));
+                HIP_TRY(hipGetLastError());
+            }
+            HIP_TRY(hipEventRecord(c->ev_join, c->st2)); HIP_TRY(hipStreamWaitEvent(st, c->ev_join, 0));
+            if (c->profiling) HIP_TRY(hipEventRecord(c->entropy[ci].start, st));
+            hipLaunchKernelGGL(k_zstd_entropy, dim3(m_n), dim3(64), 0, st, kx_entropy_sweep_args(e, rec, c->profiling ? c->sweep_rec + 1 + nt : nullptr));
+            HIP_TRY(hipGetLastError());
+            if (c->profiling) HIP_TRY(hipEventRecord(c->entropy[ci].end, st));
+            c->last_sweeps = nt + 1;
+            continue;
+        }
         hipStream_t es = st;
         if (ci + 1 < chunks) { es = c->st2; HIP_TRY(hipStreamWaitEvent(es, c->match[ci].end, 0)); forked = true; }
         if (c->profiling) HIP_TRY(hipEventRecord(c->entropy[ci].start, es));

@@ -178,6 +178,10 @@ struct kmp_batch_ctx {
     int tune_state = 0; int tune_pending = 0; u32 tune_pick = 0; float tune_ms[2] = { 0, 0 }; kmp_span tune;
     // zstd compress pipeline: entropy coding of chunk i (second stream) runs beside the match kernel of chunk i+1
     hip_stream st2; hip_event ev_join; u32 last_chunks = 0;
+    // ... or, with one launch of each kernel, entropy sweeps on the second stream beside the parse (zstd_compress_dfast; KSweepRecords).
+    // sweep_rec: the count, a counter per sweep (profiling), then done[n] and coded[n] of the running batch; ev_fork: where the
+    // second stream starts, behind the batch's clears; last_sweeps: sweep launches of the last batch, the final one included (0: none)
+    dev_buf<u32> sweep_rec; hip_event ev_fork; int can_wait_value = 0; u32 last_sweeps = 0;
     hip_event ev_pre[KMP_MAX_CHUNKS + 1];         // decoder: [0] where the caller's stream stands, [1 + i] piece i pre-decoded
     // profiling: each group of named events with its own valid flag.  match[i].end also marks where chunk i's entropy launch may start.
     int profiling = 0;
@@ -203,7 +207,7 @@ struct kmp_batch_ctx {
     hip_event ev_piece[KMP_MAX_PIECES]; u32 pieces_pending = 0;
     // experiment switches, read from the environment once, when the context is created
     struct { u32 chunks, match_flags, entropy_pad, first_permille, fast_first_permille, entropy_flags, decode_flags, decode_pad, big_rounds, big_spw,
-                 dfl_chunk, dfl_chain_waves, dfl_serial, dfl_flags, decode_pre, decode_sort, decode_pieces, decode_stage_slices, inflate_pre, inflate_pieces, autotune, match_v2, fuse; } knob = {};
+                 dfl_chunk, dfl_chain_waves, dfl_serial, dfl_flags, decode_pre, decode_sort, decode_pieces, decode_stage_slices, inflate_pre, inflate_pieces, autotune, match_v2, fuse, sweeps, sweep_min; } knob = {};
 };
 
 // The batch entry points' argument check.  fn: the name the message carries (an entry point may report for the one it serves).

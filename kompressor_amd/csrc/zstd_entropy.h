@@ -28,8 +28,10 @@ struct KEntropyArgs {
     u8* dst; const u64* out_off; u32* out_len;
     const KDictPrior* prior = nullptr;       // k_zstd_entropy_prior only: the formatted dictionary's tables
     u32 flags;                               // KXE_* below
+    // KXE_SWEEP: the parse's completion records (KMatchArgs.done), which slices a sweep has coded, and (optional) where a sweep counts them
+    const u32* done = nullptr; u32* coded = nullptr; u32* swept = nullptr;
 };
-// KEntropyArgs.flags (the low twelve bits travel on to kzstd_sequences as its xflags)
+// KEntropyArgs.flags (the low eleven bits travel on to kzstd_sequences as its xflags)
 enum : u32 {
     KXE_NO_LIT_CODING  = 1u,                 // timing experiments only (results become wrong): no literal coding,
     KXE_NO_SEQ_CODING  = 2u,                 //   no sequence coding,
@@ -39,8 +41,10 @@ enum : u32 {
     KXE_RAW_LITS       = 64u,                // literals are left uncompressed (negative levels: ZSTD_literalsCompressionIsDisabled)
     KXE_STRATEGY_SHIFT = 8u,                 // three bits: the strategy's number when it is another (3 greedy, 4 lazy, 5 lazy2).  No caller sets
     KXE_STRATEGY_MASK  = 7u,                 //   them: the kernel writes them per slice from the level below and the slice's size
+    KXE_SWEEP          = 0x800u,             // a sweep beside (or behind) the parse: a workgroup codes its slice only if the parse has finished it
+                                             //   (done) and no earlier sweep has coded it (coded), and marks it coded; otherwise it returns at once
     KXE_LEVEL_SHIFT    = 12u,                // from here up: the level (4 .. 10), or 0: every slice is of the strategy the bits above say
-    KXE_XFLAGS_MASK    = 0xFFFu,             // what kzstd_sequences gets
+    KXE_XFLAGS_MASK    = 0x7FFu,             // what kzstd_sequences gets
 };
 
 #define KXE_ERR 0xFFFFFFFFu
@@ -1615,7 +1619,13 @@ KX_DEV void zstd_entropy_body(const KEntropyArgs& a)
     int const lane = kx_lane();
     for (u32 it = kx_block(); it < a.n_slices; it += kx_nblocks()) {
         u32 const slice = kx_xcd_chunk(it, a.n_slices);
+        if (!PRIOR && (a.flags & KXE_SWEEP)) {
+            // (the same words for every lane: wave-uniform.  coded is written by sweeps only, which run one after the other)
+            if (kx_ld_agent(a.done + slice) == 0u || a.coded[slice] != 0u) continue;
+            kx_fence_acquire_agent();                           // the slice's sequences and record as the parse left them
+        }
         zstd_entropy_slice<PRIOR>(a, lds, slice, lane);
         kx_sync();
+        if (!PRIOR && (a.flags & KXE_SWEEP) && lane == 0) { a.coded[slice] = 1u; if (a.swept) kx_atomic_add(a.swept, 1u); }
     }
 }

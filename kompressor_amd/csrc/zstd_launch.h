@@ -125,6 +125,28 @@ inline KEntropyArgs kx_entropy_args(KBatchView const& v, u32 flags, const KDictP
     return e;
 }
 
+// Entropy sweeps beside a one-block parse (zstd_compress_dfast): the parse leaves a completion record per slice and counts them
+// (KMatchArgs.done / done_count); a sweep is the entropy launch with KXE_SWEEP, which codes the slices that are done and not yet
+// coded.  done, coded: one word per slice; count: one word; all zeroed before the parse is launched.
+struct KSweepRecords { u32* done; u32* coded; u32* count; };
+enum { KX_MAX_SWEEPS = 16 };
+inline void kx_match_records(KMatchArgs& m, KSweepRecords const& r) { m.done = r.done; m.done_count = r.count; }
+// swept: where the sweep counts the slices it codes, or null
+inline KEntropyArgs kx_entropy_sweep_args(KEntropyArgs e, KSweepRecords const& r, u32* swept) { e.flags |= KXE_SWEEP; e.done = r.done; e.coded = r.coded; e.swept = swept; return e; }
+// The counts of finished slices at which the K - 1 sweeps beside the parse start: T_j = j n / K, j = 1 .. K - 1, without those that are 0
+// and without duplicates (K > n), ascending; every one satisfies 0 < T <= n, so the parse reaches it.  Returns how many (< KX_MAX_SWEEPS).
+inline u32 kx_sweep_thresholds(u32 n, u32 K, u32* T)
+{
+    if (K > KX_MAX_SWEEPS) K = KX_MAX_SWEEPS;
+    u32 cnt = 0;
+    for (u32 j = 1; j < K; j++) {
+        u32 const t = (u32)((u64)j * n / K);
+        if (t == 0 || t > n || (cnt && T[cnt - 1] == t)) continue;
+        T[cnt++] = t;
+    }
+    return cnt;
+}
+
 // Frames of several blocks.  strategy: 0 level 3 / 4 (double-fast), 1 level 1 and the negative levels (fast; fast_step0 = 1 - level for
 // those, else 0), 2 level 2 (fast, but double-fast for 128 KiB < size <= 256 KiB when the size is known).  level -> these three:
 struct KBigLevel { u32 strategy, fast_step0; bool level4; };

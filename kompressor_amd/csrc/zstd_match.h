@@ -44,6 +44,10 @@ struct KMatchArgs {
     // a piece of a batch on a stream of its own (kmp_zstd_compress_batch_pieces): this launch's workgroups own the teams from
     // block_base * (64 / G) on, so that the pieces of one batch run side by side over disjoint team tables
     u32 block_base = 0;
+    // one-block mode, optional (both or neither): completion records for a launch that codes finished slices beside this one (the
+    // entropy sweeps, zstd_entropy_body).  done[slice] becomes 1 once the slice's sequences and record are in memory, then
+    // done_count goes up by one.  Zeroed by the host before the launch, which sets KXM_NO_LITS with them.
+    u32* done = nullptr; u32* done_count = nullptr;
 };
 
 // KMatchArgs.flags (every parser: zstd_match*.h; KFastArgs.m / KDictArgs.m / KBigArgs.m carry the same word)
@@ -175,8 +179,9 @@ KX_DEV void zstd_match_body(const KMatchArgs& a, DONE const& done = DONE())
     u32 tag = 0; u32 hbL = 16, hbS = 15, mls = 5;
     u32 guard = 0; u32 status = 0;
     KSeqSink sink = { a.seqs }; u8* lits = a.lits;
+    sink.wt = !BLK && a.done != nullptr;
     // pending match
-    int m_type = 0, m_pos = 0, m_start = 0, m_mpos = 0; u32 m_len0 = 0, m_off = 0, m_idxl1 = 0; u64 m_w1 = 0;
+    int m_type = 0, m_pos = 0, m_start = 0, m_mpos = 0; u32 m_idxl1 = 0; u64 m_w1 = 0;
     // long-table lookup of the first position of the next step, when the last step's extra lane already made it
     bool carry = false; u32 carry_idxl = 0;
     // KXM_ADAPTIVE (experiment): the speculation width follows the last hit -- after a hit at lane w the next step looks at
@@ -273,7 +278,7 @@ KX_DEV void zstd_match_body(const KMatchArgs& a, DONE const& done = DONE())
                         S[kx_hash_short(w, hbS, mls)] = v | (wide ? 0u : kx_chk_short(w) << CHKS);
                         L[kx_hash_long(w, hbL)] = v | (wide ? 0u : kx_chk_long(w, hbL) << CHKS);
                     }
-                    m_type = KMT_REP0; m_pos = ip; m_start = ip; m_mpos = ip - (int)off2; m_len0 = 4;
+                    m_type = KMT_REP0; m_pos = ip; m_start = ip; m_mpos = ip - (int)off2;
                     have_pw = false;
                     state = KST_MATCH;
                 } else {
@@ -399,11 +404,9 @@ KX_DEV void zstd_match_body(const KMatchArgs& a, DONE const& done = DONE())
                     if (K == 0 || guard > 2u * (u32)n + 64u) { status = 1; state = KST_CLEANUP; }
                 } else {
                     m_type = b_type; m_pos = ip + wl * step;
-                    if (b_type == KMT_REP) { m_start = m_pos + 1; m_mpos = m_start - (int)off1; m_len0 = 4; }
+                    if (b_type == KMT_REP) { m_start = m_pos + 1; m_mpos = m_start - (int)off1; }
                     else {
-                        if (b_type == KMT_LONG) { m_start = m_pos; m_mpos = (int)b_idxl - 2; m_len0 = 8; }
-                        else { m_start = m_pos; m_mpos = (int)b_idxs - 2; m_len0 = 4; }
-                        m_off = (u32)(m_start - m_mpos);
+                        m_start = m_pos; m_mpos = (int)(b_type == KMT_LONG ? b_idxl : b_idxs) - 2;
                         m_idxl1 = n_idxl; m_w1 = (u64)n_wlo | ((u64)n_whi << 32);
                         if (step < 4 && k == 0) L[n_hl] = tag | (u32)(m_pos + step + 2) | (wide ? 0u : kx_chk_long(m_w1, hbL) << CHKS);
                     }
@@ -432,12 +435,13 @@ KX_DEV void zstd_match_body(const KMatchArgs& a, DONE const& done = DONE())
             int const mb0 = (m_start - anchor < mlow0) ? m_start - anchor : mlow0;
             u32 bs0 = 0, bm0 = 0;
             if (bw0 && k < mb0) { bs0 = src[m_start - 1 - k]; bm0 = src[m_mpos - 1 - k]; }
-            u32 lenA = kx_team_extend<G>(mt, src, n, m_start, m_mpos, m_len0, k, tbase, tmask);
+            // (the bytes the search compared: 8 of a long-table hit, else 4; the offset of a table hit is m_start - m_mpos throughout)
+            u32 lenA = kx_team_extend<G>(mt, src, n, m_start, m_mpos, m_type == KMT_LONG ? 8u : 4u, k, tbase, tmask);
             bool const l1ok = l1cand && l1v == m_w1;
             bool tookB = false;
             if (kx_any(l1ok)) {
                 u32 const lenB = kx_team_extend<G>(l1ok, src, n, s1, m1, 8u, k, tbase, tmask);
-                if (l1ok && lenB > lenA) { m_start = s1; m_mpos = m1; lenA = lenB; m_off = (u32)(s1 - m1); tookB = true; }
+                if (l1ok && lenB > lenA) { m_start = s1; m_mpos = m1; lenA = lenB; tookB = true; }
             }
             bool const bw = mt && (m_type == KMT_LONG || m_type == KMT_SHORT);
             int const mlow = m_mpos - ((int)lowIdx - 2);               // the match may grow backwards down to the lowest valid position
@@ -445,7 +449,7 @@ KX_DEV void zstd_match_body(const KMatchArgs& a, DONE const& done = DONE())
             u32 const back = kx_team_backward<G>(bw, src, m_start, m_mpos, mb, k, tbase, tmask, !tookB, bs0, bm0);
             if (mt) {
                 u32 offBase = 1;
-                if (bw) { m_start -= (int)back; m_mpos -= (int)back; lenA += back; off2 = off1; off1 = m_off; offBase = m_off + 3; }
+                if (bw) { m_start -= (int)back; m_mpos -= (int)back; lenA += back; off2 = off1; off1 = (u32)(m_start - m_mpos); offBase = off1 + 3; }
                 else if (m_type == KMT_REP0) { u32 const t = off2; off2 = off1; off1 = t; }
                 int const ll = m_start - anchor;
                 if (!(a.flags & KXM_NO_LITS)) for (int c = 8 * k; c < ll; c += 8 * G) kx_st64(lits + sink.nlit + c, kx_ld64_clamped(src, anchor + c, n));
@@ -472,9 +476,22 @@ KX_DEV void zstd_match_body(const KMatchArgs& a, DONE const& done = DONE())
                         u32 const s2 = (saved1 != 0 && off1 != 0) ? saved1 : saved2;
                         mm.pad[0] = off1 ? off1 : saved1; mm.pad[1] = off2 ? off2 : s2;
                     }
-                    a.meta[slice] = mm;
+                    if (sink.wt) { u64 w[4]; __builtin_memcpy(w, &mm, 32); for (int i = 0; i < 4; i++) kx_st64_agent((u64*)(a.meta + slice) + i, w[i]); }
+                    else a.meta[slice] = mm;
                 }
                 state = KST_IDLE;
+            }
+            // The completion record.  Every slice index the claim hands out enters KST_CLEANUP exactly once -- straight from the claim
+            // when the slice is empty, shorter than 8 bytes or refused by the level, from the search and the match blocks when the
+            // parse ends or a runaway guard trips -- and leaves it here: done_count reaches n_slices in every launch, which is
+            // what the host's stream waits on it rely on (a count that fell short would leave a stream waiting for ever).
+            // (the sequences and the record went out with agent-scope stores: KSeqSink.wt.  The literals do not: the launch asks for
+            // KXM_NO_LITS.)
+            if (!BLK && a.done) {
+                kx_wait_stores();                               // the team's sequences and record before its flag ...
+                if (fin && k == 0) kx_st_agent(a.done + slice, 1u);
+                kx_wait_stores();                               // ... and the flag before the count
+                if (fin && k == 0) kx_atomic_add(a.done_count, 1u);
             }
             if (DONE::on) {
                 u64 fm = kx_ballot(fin && k == 0);
@@ -484,7 +501,7 @@ KX_DEV void zstd_match_body(const KMatchArgs& a, DONE const& done = DONE())
                 // land inside the search loop).
                 u32 sv[64];
 #define KX_MS32(X) X(state) X(n) X(ilimit) X(slice) X(ip) X(anchor) X(off1) X(off2) X(step) X(nextStep) X(sink.nseq) X(sink.nlit) X(tag) X(hbL) X(hbS) X(mls) \
-                   X(sink.longType) X(sink.longPos) X(guard) X(status) X(m_type) X(m_pos) X(m_start) X(m_mpos) X(m_len0) X(m_off) X(m_idxl1) X(carry_idxl) X(kmax) \
+                   X(sink.longType) X(sink.longPos) X(guard) X(status) X(m_type) X(m_pos) X(m_start) X(m_mpos) X(m_idxl1) X(carry_idxl) X(kmax) \
                    X(c_pos) X(lowIdx) X(bstart) X(saved1) X(saved2)
 #define KX_MS64(X) X(m_w1) X(sink.sq0) X(sink.sq1) X(wa) X(pw)
 #define KX_MSP(X) X(src) X(sink.seqs) X(lits) X(L) X(S)

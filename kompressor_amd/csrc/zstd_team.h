@@ -10,6 +10,7 @@
 // the body.  All cross-lane primitives are called from wave-uniform control flow.
 #pragma once
 #include "zstd_common.h"
+#include "kx_agent.h"
 
 // ---- the lane inside its team ------------------------------------------
 // k: index inside the team; tbase: the wave lane of the team's lane 0; tmask: G ones; team: the team's index in the
@@ -67,8 +68,10 @@ KX_DEV u32 kx_team_tag(int k, u32 ep, u32* tbl, u32 entries)
 // ---- the sequence sink --------------------------------------------------
 // Sequences wait in registers (two per lane) until the team can store whole 16-byte pieces of a line; uniform across
 // the team's lanes except sq0 / sq1.
+// wt: the stores go through the L2 at once (kx_st64_agent), for a launch that reads the slice while this one still runs (the
+// parse's completion records, zstd_match.h); uniform across the wave
 struct KSeqSink {
-    KSeq* seqs; u64 sq0, sq1; u32 nseq, nlit, longType, longPos;
+    KSeq* seqs; u64 sq0, sq1; u32 nseq, nlit, longType, longPos; bool wt = false;
 
     KX_MEMBER void reset(KSeq* s) { seqs = s; nseq = 0; nlit = 0; longType = 0; longPos = 0; }
 
@@ -78,7 +81,10 @@ struct KSeqSink {
         u64 const q = (u64)offBase | ((u64)(u16)ll << 32) | ((u64)(u16)mlBase << 48);   // KSeq
         u32 const slot = nseq & (2u * G - 1u);
         if ((u32)k == (slot >> 1)) { if (slot & 1u) sq1 = q; else sq0 = q; }
-        if (slot == 2u * G - 1u) kx_st128(seqs + (nseq - slot) + 2u * (u32)k, sq0, sq1);
+        if (slot == 2u * G - 1u) {
+            KSeq* const p = seqs + (nseq - slot) + 2u * (u32)k;
+            if (wt) { kx_st64_agent((u64*)p, sq0); kx_st64_agent((u64*)p + 1, sq1); } else kx_st128(p, sq0, sq1);
+        }
         if (ll > 0xFFFF) { longType = 1; longPos = nseq; }
         if (mlBase > 0xFFFF) { longType = 2; longPos = nseq; }
         nseq++; nlit += (u32)ll;
@@ -90,8 +96,8 @@ struct KSeqSink {
     {
         u32 const cnt = nseq & (2u * G - 1u);
         u64* const sp = (u64*)(seqs + (nseq - cnt));
-        if (2u * (u32)k < cnt) sp[2 * k] = sq0;
-        if (2u * (u32)k + 1u < cnt) sp[2 * k + 1] = sq1;
+        if (2u * (u32)k < cnt) { if (wt) kx_st64_agent(sp + 2 * k, sq0); else sp[2 * k] = sq0; }
+        if (2u * (u32)k + 1u < cnt) { if (wt) kx_st64_agent(sp + 2 * k + 1, sq1); else sp[2 * k + 1] = sq1; }
     }
 
     // the slice's record; the padding words are the body's (repcodes of a block, timestamps)
