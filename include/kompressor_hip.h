@@ -543,6 +543,79 @@ KMP_API uint32_t kmp_zstd_seekable_read_frames(const kmp_seekable* h, uint64_t l
 KMP_API int kmp_zstd_seekable_read(kmp_seekable* h, const void* d_blob, uint64_t lo, uint64_t hi, int verify, void* d_dst, size_t dst_cap,
                                    uint64_t* skip, uint32_t* d_status, void* hip_stream);
 
+/* BGZF containers (SAM specification 4.1; bgzip, htslib, Bio.bgzf; no reference counterpart: the reference compresses one slice per
+ * call): the zlib twin of the seekable container.  ONE large buffer cut into blocks of block_bytes each, every block a gzip member of its
+ * own whose extra field carries the member's size, then an empty member as the end-of-file marker.  Any gzip reader (gunzip, Python's gzip)
+ * reads the container as ordinary multi-member gzip; a BGZF reader fetches a byte range by decoding only the members that cover it.  All
+ * fields little-endian:
+ *   member = 1f 8b 08 04 | MTIME 00000000 | XFL 00 | OS ff | XLEN 0006 | 'B' 'C' 02 00 | BSIZE u16 = member bytes - 1
+ *            | raw DEFLATE payload | CRC32 u32 | ISIZE u32
+ *   marker = 1f8b08040000000000ff0600424302001b0003000000000000000000          (28 bytes)
+ * The payloads are bit for bit those kmp_deflate_compress_batch_level(format 0, level) writes for the blocks (zlib 1.2.11's
+ * deflateInit2(level, Z_DEFLATED, -15, 8, Z_DEFAULT_STRATEGY)), so the whole container is determined byte for byte by (input, block_bytes,
+ * level). */
+#define KMP_BGZF_NO_EOF 1u     /* leave the marker out: rounds over a larger buffer are concatenated by the caller (BGZF files concatenate) */
+/* room a container of src_size bytes needs: kmp_deflate_bound + 8 of every block, plus the marker (0: block_bytes outside 1 .. 65 280) */
+KMP_API size_t kmp_bgzf_bound(size_t src_size, uint32_t block_bytes, uint32_t flags);
+/* device scratch (8-byte aligned) the compress call wants from its caller: the members at bound-sized strides before they are packed and
+ * the blocks' offset and length arrays.  The context allocates nothing for this feature beyond the DEFLATE workspace the batch call
+ * itself takes on its first use. */
+KMP_API size_t kmp_bgzf_scratch(size_t src_size, uint32_t block_bytes);
+/* d_src[0 .. src_size) -> the container at d_dst (dst_cap >= kmp_bgzf_bound, else KMP_ERR_CAPACITY).  Asynchronous on hip_stream, no host
+ * wait: plan, the raw DEFLATE batch at `level` (1 .. 9, -1 = 6; else KMP_ERR_ARG), header, CRC-32 and ISIZE around every payload,
+ * kmp_compact_batch's packing, the marker.  block_bytes: 1 .. 65 280 (else KMP_ERR_ARG; 65 280 is htslib's) and at most the context's
+ * max_slice_bytes; the blocks, ceil(src_size / block_bytes), at most its max_slices (else KMP_ERR_CAPACITY: cut a larger buffer into
+ * rounds with KMP_BGZF_NO_EOF on all but the last and concatenate).  d_result (device, 8-byte aligned): [0] = the container's size, or 0
+ * when a block got no member; [1] = the context's KMP_STATUS_* bits as they stand.  An empty input gives the marker alone, or nothing
+ * with KMP_BGZF_NO_EOF. */
+KMP_API int kmp_bgzf_compress(kmp_batch_ctx* ctx, const void* d_src, size_t src_size, uint32_t block_bytes, int level, uint32_t flags,
+                              void* d_dst, size_t dst_cap, void* d_scratch, size_t scratch_bytes, uint64_t* d_result /* [2] */, void* hip_stream);
+/* What following the members from offset 0 finds.  status is zlib's number: 0 good; -3 (Z_DATA_ERROR) a head that is no BGZF member's
+ * (magic, XLEN below 6, a subfield past XLEN, BC missing, doubled or of another length than 2, a BSIZE too small for its own header, an
+ * ISIZE above 65 536); -5 (Z_BUF_ERROR) the blob ends inside a member, or is empty.  With a status every other field is 0. */
+typedef struct {
+    uint64_t content;         /* decompressed bytes of the whole container */
+    uint32_t blocks;          /* members, empty ones and the marker included */
+    uint32_t max_block;       /* the largest ISIZE */
+    uint32_t max_compressed;  /* the largest member */
+    uint32_t flags;           /* bit 0: the last member is the end-of-file marker; bit 1: some member has extra subfields besides BC */
+    int32_t  status;
+    uint32_t reserved;
+} kmp_bgzf_stat;              /* 32 bytes */
+typedef struct kmp_bgzf kmp_bgzf;
+/* Finds the members of d_blob[0 .. blob_size) (device memory) on the device.  BGZF has no table: a serial reader follows the size fields
+ * from offset 0, one dependent memory read per member.  This call reads the blob once in parallel, tests a member's head wherever the
+ * magic stands (candidates, false ones inside compressed data included), links every candidate to the one its size points at, and marks
+ * the chain from offset 0 by pointer doubling.  Two host waits: the candidates' count (the tables are allocated to it), then the stat and
+ * the prefix sums of both sizes, kept in the handle on the host and, as the arrays kmp_inflate_batch takes, on the device (36 bytes per
+ * member).  Above 2^20 candidates (or a blob of 64 GiB) the members are followed by one lane instead.  Either way the answer is the
+ * serial walk's, byte for byte.  A damaged blob still gives a handle (KMP_OK): stat tells, and reads are refused.  A handle serves one
+ * stream at a time and must be closed before its context is destroyed. */
+KMP_API int kmp_bgzf_open(kmp_batch_ctx* ctx, const void* d_blob, size_t blob_size, kmp_bgzf** out, void* hip_stream);
+KMP_API void kmp_bgzf_close(kmp_bgzf* h);
+KMP_API int kmp_bgzf_stat_of(const kmp_bgzf* h, kmp_bgzf_stat* stat);
+/* The serial walk over a blob in HOST memory: the same code compiled for the host, no GPU touched, no context needed.  member_off /
+ * content_off (each may be NULL): where every member starts in the blob / in the content, blocks + 1 entries each (the last: the blob's
+ * size, the content's), written when the status is 0 and prefix_cap >= blocks + 1. */
+KMP_API int kmp_bgzf_index_host(const void* h_blob, size_t blob_size, kmp_bgzf_stat* stat, uint64_t* member_off, uint64_t* content_off, size_t prefix_cap);
+/* bytes a read of [lo, hi) writes: the covering members whole (hi is cut at the content's end; 0 for an empty range or one past the end) */
+KMP_API size_t kmp_bgzf_read_bound(const kmp_bgzf* h, uint64_t lo, uint64_t hi);
+/* ... and how many members cover it (0 for such a range): the statuses a read writes; *first (may be NULL) = the first one's index */
+KMP_API uint32_t kmp_bgzf_read_blocks(const kmp_bgzf* h, uint64_t lo, uint64_t hi, uint32_t* first);
+/* Decodes the members that cover [lo, hi), whole and back to back, into d_dst (dst_cap >= kmp_bgzf_read_bound, else KMP_ERR_CAPACITY):
+ * their raw payloads go through kmp_inflate_batch (format 0) on the handle's context with the ISIZEs as capacities -- a gzip member with
+ * an extra field would miss that call's two-kernel path --, then every trailer is checked on the device.  *skip = lo minus the first
+ * covering member's start: the bytes asked for are d_dst[*skip .. *skip + hi - lo).  Nothing is read back, the call is asynchronous;
+ * more covering members than the context's max_slices go through in rounds.  d_status (device, one int32 per covering member:
+ * kmp_bgzf_read_blocks says how many): 0, or zlib's number as kmp_inflate_batch gives it; a member that decoded cleanly to another size
+ * than its ISIZE gets -3, and with verify != 0 one whose CRC-32 differs from its trailer -3 as well.  d_blob: the container the handle was
+ * opened over.  An empty range or one past the end is KMP_OK with nothing written; a handle whose status is not 0 is KMP_ERR_ARG. */
+KMP_API int kmp_bgzf_read(kmp_bgzf* h, const void* d_blob, uint64_t lo, uint64_t hi, int verify, void* d_dst, size_t dst_cap,
+                          uint64_t* skip, int32_t* d_status, void* hip_stream);
+/* BGZF's virtual offset of content position content_pos: the start of the member that holds it << 16 | its offset inside the member's
+ * content.  content_pos == the content's size gives the blob's size << 16; beyond it, or a handle with a status, ~0. */
+KMP_API uint64_t kmp_bgzf_tell(const kmp_bgzf* h, uint64_t content_pos);
+
 /* Per-kernel device time of the last batch call, measured with HIP events on the
  * launch stream (0 = off, 1 = on).  kmp_batch_last_kernel_ms synchronises. */
 KMP_API int kmp_batch_set_profiling(kmp_batch_ctx* ctx, int on);

@@ -74,6 +74,17 @@ SIGNATURES = [
     ("kmp_zstd_seekable_read_bound", _c.c_size_t, [_P, _c.c_uint64, _c.c_uint64]),
     ("kmp_zstd_seekable_read_frames", _c.c_uint32, [_P, _c.c_uint64, _c.c_uint64, _c.POINTER(_c.c_uint32)]),
     ("kmp_zstd_seekable_read", _c.c_int, [_P, _P, _c.c_uint64, _c.c_uint64, _c.c_int, _P, _c.c_size_t, _c.POINTER(_c.c_uint64), _P, _P]),
+    ("kmp_bgzf_bound", _c.c_size_t, [_c.c_size_t, _c.c_uint32, _c.c_uint32]),
+    ("kmp_bgzf_scratch", _c.c_size_t, [_c.c_size_t, _c.c_uint32]),
+    ("kmp_bgzf_compress", _c.c_int, [_P, _P, _c.c_size_t, _c.c_uint32, _c.c_int, _c.c_uint32, _P, _c.c_size_t, _P, _c.c_size_t, _P, _P]),
+    ("kmp_bgzf_open", _c.c_int, [_P, _P, _c.c_size_t, _c.POINTER(_P), _P]),
+    ("kmp_bgzf_close", None, [_P]),
+    ("kmp_bgzf_stat_of", _c.c_int, [_P, _P]),
+    ("kmp_bgzf_index_host", _c.c_int, [_P, _c.c_size_t, _P, _P, _P, _c.c_size_t]),
+    ("kmp_bgzf_read_bound", _c.c_size_t, [_P, _c.c_uint64, _c.c_uint64]),
+    ("kmp_bgzf_read_blocks", _c.c_uint32, [_P, _c.c_uint64, _c.c_uint64, _c.POINTER(_c.c_uint32)]),
+    ("kmp_bgzf_read", _c.c_int, [_P, _P, _c.c_uint64, _c.c_uint64, _c.c_int, _P, _c.c_size_t, _c.POINTER(_c.c_uint64), _P, _P]),
+    ("kmp_bgzf_tell", _c.c_uint64, [_P, _c.c_uint64]),
     ("kmp_batch_set_profiling", _c.c_int, [_P, _c.c_int]),
     ("kmp_batch_last_kernel_ms", _c.c_int, [_P, _c.c_int, _c.POINTER(_c.c_float)]),
     ("kmp_batch_last_chunks", _c.c_int, [_P]),
@@ -102,6 +113,11 @@ class BatchOptions(_c.Structure):          # kmp_batch_options
 class SeekableStat(_c.Structure):         # kmp_seekable_stat
     _fields_ = [("content", _c.c_uint64), ("table_off", _c.c_uint64), ("frames", _c.c_uint32), ("max_frame", _c.c_uint32),
                 ("max_compressed", _c.c_uint32), ("flags", _c.c_uint32), ("status", _c.c_uint32), ("reserved", _c.c_uint32)]
+
+
+class BgzfStat(_c.Structure):             # kmp_bgzf_stat
+    _fields_ = [("content", _c.c_uint64), ("blocks", _c.c_uint32), ("max_block", _c.c_uint32), ("max_compressed", _c.c_uint32),
+                ("flags", _c.c_uint32), ("status", _c.c_int32), ("reserved", _c.c_uint32)]
 
 
 class BatchMemoryInfo(_c.Structure):       # kmp_batch_memory_info

@@ -180,6 +180,77 @@ class SeekableReader:
         return self.read(0, self.content_size, verify)
 
 
+class BgzfReader:
+    """A BGZF container in device memory, opened by ZstdBatch.open_bgzf (kmp_bgzf_open: the members are found on the device, the stat and
+    both prefix sums read back).  stat: the _lib.BgzfStat; status is zlib's number for a blob that was rejected (-3 or -5: then every
+    read raises)."""
+
+    def __init__(self, batch, blob):
+        self.batch, self.blob = batch, blob
+        h = ctypes.c_void_p()
+        rc = batch.lib.kmp_bgzf_open(batch._h, _ptr(blob) if blob.numel() else None, blob.numel(), ctypes.byref(h), batch._stream())
+        if rc != 0:
+            raise RuntimeError(f"kmp_bgzf_open failed ({rc}): {batch._err()}")
+        self._h = h
+        self.stat = _lib.BgzfStat()
+        batch.lib.kmp_bgzf_stat_of(h, ctypes.byref(self.stat))
+        self.status, self.blocks, self.content_size = int(self.stat.status), int(self.stat.blocks), int(self.stat.content)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self.batch.lib.kmp_bgzf_close(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def tell(self, pos):
+        """BGZF's virtual offset of content position pos (kmp_bgzf_tell): member start << 16 | offset inside the member's content"""
+        v = self.batch.lib.kmp_bgzf_tell(self._h, pos)
+        if v == (1 << 64) - 1:
+            raise ValueError(f"position {pos} lies outside the content, or the blob was rejected")
+        return v
+
+    def read_blocks(self, lo, hi, verify=True):
+        """kmp_bgzf_read, queued with no host wait: the members covering [lo, hi) decoded whole into one buffer.
+        -> (dst, skip, status): the bytes asked for are dst[skip : skip + hi - lo]; status: int32 device tensor, one per covering member
+        (0, zlib's number, -3 for a size or -- under verify -- a CRC-32 that does not match the trailer)."""
+        lib, b = self.batch.lib, self.batch
+        if self.status:
+            raise RuntimeError(f"the BGZF blob was rejected (status {self.status})")
+        need = lib.kmp_bgzf_read_bound(self._h, lo, hi)
+        m = lib.kmp_bgzf_read_blocks(self._h, lo, hi, None)
+        dst = torch.empty(need + 64, dtype=torch.uint8, device=b.device)
+        status = torch.zeros(max(m, 1), dtype=torch.int32, device=b.device)
+        skip = ctypes.c_uint64()
+        rc = lib.kmp_bgzf_read(self._h, _ptr(self.blob), lo, hi, 1 if verify else 0, _ptr(dst), need, ctypes.byref(skip), _ptr(status), b._stream())
+        if rc != 0:
+            raise RuntimeError(f"kmp_bgzf_read failed ({rc}): {b._err()}")
+        return dst, int(skip.value), status[:m]
+
+    def read(self, lo, hi, verify=True):
+        """Bytes [lo, hi) of the content (hi is cut at the content's end): a uint8 device tensor view of exactly that many bytes.
+        verify: compare every decoded member's CRC-32 with its trailer.  Reads the members' statuses back (a host wait) and raises on a
+        nonzero one."""
+        if self.status:
+            raise RuntimeError(f"the BGZF blob was rejected (status {self.status})")
+        hi = min(hi, self.content_size)
+        if lo >= hi:
+            return torch.empty(0, dtype=torch.uint8, device=self.batch.device)
+        dst, skip, status = self.read_blocks(lo, hi, verify)
+        bad = torch.nonzero(status).flatten().tolist()
+        if bad:
+            codes = status.tolist()
+            raise RuntimeError(f"BGZF read [{lo}, {hi}): member status " + ", ".join(f"+{i}: {codes[i]}" for i in bad[:8]))
+        return dst[skip:skip + hi - lo]
+
+    def read_all(self, verify=True):
+        return self.read(0, self.content_size, verify)
+
+
 class ZstdBatch:
     """Owns the device workspace for batches of up to `max_slices` slices of up to
     `max_slice_bytes` bytes (<= 128 KiB) on one GPU."""
@@ -346,6 +417,34 @@ class ZstdBatch:
     def open_seekable(self, blob):
         """A SeekableReader over a container in device memory (uint8 tensor; it must stay alive while the reader is used)."""
         return SeekableReader(self, blob)
+
+    def compress_bgzf(self, src, block_bytes=65280, level=6, eof=True):
+        """One buffer (uint8 device tensor) -> a BGZF container (kmp_bgzf_compress): a gzip member per block of block_bytes (1 .. 65 280,
+        at most the context's max_slice_bytes; at most max_slices of them) at zlib's `level` (1 .. 9, -1 = 6), then the end-of-file
+        marker unless eof is False (rounds over a larger buffer: concatenate them, the last one with eof).  gunzip and every BGZF reader
+        decode the result; open_bgzf reads byte ranges of it.  Returns a uint8 device tensor trimmed to the container: the one host
+        wait is the .item() that reads its size to trim it."""
+        n = src.numel()
+        flags = 0 if eof else 1
+        cap = self.lib.kmp_bgzf_bound(n, block_bytes, flags)
+        need = self.lib.kmp_bgzf_scratch(n, block_bytes)
+        if need == 0:
+            raise ValueError("block_bytes must be 1 .. 65280")
+        dst = torch.empty(cap + 64, dtype=torch.uint8, device=self.device)
+        scratch = torch.empty((need + 7) // 8, dtype=torch.int64, device=self.device)
+        result = torch.zeros(2, dtype=torch.int64, device=self.device)
+        rc = self.lib.kmp_bgzf_compress(self._h, _ptr(src) if n else None, n, block_bytes, level, flags, _ptr(dst), cap, _ptr(scratch), need,
+                                        _ptr(result), self._stream())
+        if rc != 0:
+            raise RuntimeError(f"kmp_bgzf_compress failed ({rc}): {self._err()}")
+        size = int(result[0].item())
+        if size == 0 and (n or eof):
+            raise RuntimeError(f"kmp_bgzf_compress: a block got no member (status bits {int(result[1].item()):#x})")
+        return dst[:size]
+
+    def open_bgzf(self, blob):
+        """A BgzfReader over a BGZF container in device memory (uint8 tensor; it must stay alive while the reader is used)."""
+        return BgzfReader(self, blob)
 
     def piece_range(self, n, pieces, piece):
         """(first, count) of part `piece` of an n-slice batch cut into `pieces` (kmp_batch_piece_range)."""

@@ -2,7 +2,7 @@
 the product boundary is a plain C ABI).
 
   libkompressor_hip.so      hipcc, gfx950 only   -- the product: csrc/kmp_batch.hip + kmp_deflate.hip + kmp_stream.hip
-                            + kmp_seekable.hip
+                            + kmp_seekable.hip + kmp_bgzf.hip
   libkompressor_hip_abl.so  the same sources with -DKMP_ABLATIONS: the second level-3 parser, the fused kernel and the
                             experiment knobs as environment variables (what the tests of those paths and the A/B tools load)
   libkmpcorpus.so           gcc                   -- seeded synthetic corpus (bench + tests)
@@ -17,7 +17,7 @@ CSRC = os.path.join(HERE, "csrc")
 
 HIP_LIB = os.path.join(HERE, "libkompressor_hip.so")
 HIP_LIB_ABL = os.path.join(HERE, "libkompressor_hip_abl.so")
-HIP_UNITS = ("kmp_batch.hip", "kmp_deflate.hip", "kmp_stream.hip", "kmp_seekable.hip")
+HIP_UNITS = ("kmp_batch.hip", "kmp_deflate.hip", "kmp_stream.hip", "kmp_seekable.hip", "kmp_bgzf.hip")
 OBJ_DIR = os.path.join(HERE, "csrc", "_obj")
 CORPUS_LIB = os.path.join(HERE, "libkmpcorpus.so")
 
