@@ -45,6 +45,10 @@ typedef struct kmp_zstd_dctx kmp_zstd_dctx;
  * com/ensody/kompressor/zstd/ZstdParameter.kt:3-24; only 100 is ever set,
  * ZstdCompressor.jvm.kt:21) */
 #define KMP_ZSTD_c_compressionLevel 100
+/* ... and the three that shape a frame's header and trailer without touching its blocks (values 0 or 1) */
+#define KMP_ZSTD_c_contentSizeFlag  200   /* default 1; 0: no Frame_Content_Size, a window descriptor instead of the single-segment flag */
+#define KMP_ZSTD_c_checksumFlag     201   /* default 0; 1: the low 32 bits of the content's XXH64 behind the last block */
+#define KMP_ZSTD_c_dictIDFlag       202   /* default 1; 0: no Dictionary_ID field in frames parsed against a formatted dictionary */
 
 /* replaces ZSTD_createCCtx            (Wrapper.cpp:10-17)  */
 KMP_API kmp_zstd_cctx* kmp_zstd_create_cctx(void);
@@ -53,7 +57,11 @@ KMP_API size_t kmp_zstd_free_cctx(kmp_zstd_cctx* cctx);
 /* replaces ZSTD_CCtx_setParameter     (Wrapper.cpp:29-39). Levels -131072 .. -1 and 1 .. 10 (0 = default = 3) run on the GPU where
  * kmp_zstd_compress_batch_level serves them (dictionaries: level 3 only; levels 5 .. 10: streams of up to 2 MiB, or one closing call of
  * at most 128 KiB -- 9 and 10 above 16 KiB --, or of up to 2 MiB when the call's output slice has room for kmp_zstd_compress_bound of it; what
- * is not served surfaces when the stream closes); levels 11 and up return (size_t)-40 "Unsupported parameter". */
+ * is not served surfaces when the stream closes); levels 11 and up return (size_t)-40 "Unsupported parameter".
+ * Ids 200 .. 202 (above) take 0 or 1 and return the value set, as libzstd does -- not 0; any other value returns (size_t)-42 "Parameter
+ * is out of bound" (libzstd 1.5.7 itself takes every nonzero value as 1).  They hold for every frame the context writes from then on,
+ * whatever path it takes, and like the level they are refused with (size_t)-60 once input has been fed.  Every other id returns
+ * (size_t)-40. */
 KMP_API size_t kmp_zstd_cctx_set_parameter(kmp_zstd_cctx* cctx, int param, int value);
 /* replaces ZSTD_CCtx_loadDictionary   (Wrapper.cpp:41-56). Served: dictionaries of 8 .. 130 560 bytes for slices <= 128 KiB, raw content
  * or zstd's own format (magic EC30A437: what `zstd --train` / ZDICT_trainFromBuffer write -- its Huffman and FSE tables, repeat offsets
@@ -149,7 +157,7 @@ typedef struct kmp_batch_ctx kmp_batch_ctx;
  * slice gets d_out_len[i] = 0 (a frame or stream is never empty) and the context's status word collects these bits. */
 #define KMP_STATUS_SLICE_TOO_LARGE 1u   /* a d_in_len[i] above the context's max_slice_bytes (DEFLATE: above 64 KiB) */
 #define KMP_STATUS_KERNEL_GUARD    2u   /* a parser's loop guard tripped (never expected) */
-#define KMP_STATUS_LEVEL_SIZE      4u   /* the level is not served at a slice's size (level 4: 128 - 256 KiB; levels 9, 10: 8 bytes .. 16 KiB; levels 5 .. 10: above 2 MiB): out_len 0 */
+#define KMP_STATUS_LEVEL_SIZE      4u   /* the level is not served at a slice's size (level 4: up to 16 KiB on a context for slices above 128 KiB, and 128 - 256 KiB as a staged frame; levels 9, 10: 8 bytes .. 16 KiB; levels 5 .. 10: above 2 MiB): out_len 0 */
 
 #define KMP_MAX_SLICE_BYTES (128u * 1024u)        /* one block per frame: the batched fast path */
 #define KMP_MAX_BIG_SLICE_BYTES (1u << 30)       /* frames of several blocks (context created with max_slice_bytes above
@@ -183,6 +191,18 @@ KMP_API void kmp_batch_destroy(kmp_batch_ctx* ctx);
  * then clears them.  Returns KMP_OK, KMP_ERR_CAPACITY (a slice was too large) or KMP_ERR_KERNEL; *bits may be NULL.
  * A context runs one batch at a time: a batch queued on another stream waits for the previous one's last kernel. */
 KMP_API int kmp_batch_status(kmp_batch_ctx* ctx, uint32_t* bits, void* hip_stream);
+/* What the zstd compress calls write around a frame's blocks.  The flags hold for every zstd compress export run on the context
+ * afterwards -- kmp_zstd_compress_batch, _level, _dict, _dict_level, _stream, _reference and _pieces --; a fresh context has flags 0
+ * and writes ZSTD_compress2's default frames.  The setter does not wait: a batch takes the flags at the time it is queued.  Unknown
+ * bits return KMP_ERR_ARG.  The blocks of a frame are the same bytes under every flag set, a frame with its checksum still fits
+ * kmp_zstd_compress_bound(len) + 8, and the decoders verify the checksum (status 22).  A batch with KMP_FRAME_CHECKSUM runs one XXH64
+ * pass over its slices in front of its other kernels (a quad of lanes per slice, so a single very long slice is hashed at one quad's
+ * rate).  The seekable and BGZF containers ignore the flags: their frames stay as their formats specify them. */
+#define KMP_FRAME_CHECKSUM        1u   /* ZSTD_c_checksumFlag = 1 */
+#define KMP_FRAME_NO_CONTENT_SIZE 2u   /* ZSTD_c_contentSizeFlag = 0 (streaming frames never have one: nothing changes there) */
+#define KMP_FRAME_NO_DICT_ID      4u   /* ZSTD_c_dictIDFlag = 0 (a raw-content dictionary, or none: nothing changes) */
+KMP_API int kmp_batch_set_frame_flags(kmp_batch_ctx* ctx, uint32_t flags);
+KMP_API uint32_t kmp_batch_frame_flags(kmp_batch_ctx* ctx);
 
 /* zstd level-3 frames for n independent slices.  All pointers are device
  * pointers; slice i is d_src[d_in_off[i] .. +d_in_len[i]); its frame goes to

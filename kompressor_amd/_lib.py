@@ -31,6 +31,8 @@ SIGNATURES = [
     ("kmp_batch_memory", _c.c_int, [_P, _P]),
     ("kmp_batch_destroy", None, [_P]),
     ("kmp_batch_status", _c.c_int, [_P, _c.POINTER(_c.c_uint32), _P]),
+    ("kmp_batch_set_frame_flags", _c.c_int, [_P, _c.c_uint32]),
+    ("kmp_batch_frame_flags", _c.c_uint32, [_P]),
     ("kmp_zstd_compress_batch", _c.c_int, [_P, _P, _P, _P, _c.c_uint32, _P, _P, _P, _P]),
     ("kmp_batch_piece_range", None, [_c.c_uint32, _c.c_uint32, _c.c_uint32, _c.POINTER(_c.c_uint32), _c.POINTER(_c.c_uint32)]),
     ("kmp_zstd_compress_batch_pieces", _c.c_int, [_P, _P, _P, _P, _c.c_uint32, _P, _P, _P, _c.c_uint32, _P]),

@@ -343,7 +343,19 @@ class ZstdBatch:
         if rc != 0:
             raise RuntimeError(f"{what}: status bits {bits:#x} ({rc}): {self._err()}")
 
-    def compress(self, src, in_off, in_len, dst=None, out_off=None, out_len=None, dictionary=None, level=3, streaming=None, reference=False, check=False):
+    FRAME_CHECKSUM, FRAME_NO_CONTENT_SIZE, FRAME_NO_DICT_ID = 1, 2, 4          # KMP_FRAME_*
+
+    def set_frame_flags(self, flags):
+        """kmp_batch_set_frame_flags: what the zstd compress batches queued from now on write around their blocks (FRAME_* bits)."""
+        rc = self.lib.kmp_batch_set_frame_flags(self._h, flags)
+        if rc != 0:
+            raise ValueError(f"kmp_batch_set_frame_flags failed ({rc}): {self._err()}")
+
+    def frame_flags(self):
+        return int(self.lib.kmp_batch_frame_flags(self._h))
+
+    def compress(self, src, in_off, in_len, dst=None, out_off=None, out_len=None, dictionary=None, level=3, streaming=None, reference=False, check=False,
+                 checksum=False, content_size=True, dict_id=True):
         """src: uint8 device tensor; in_off int64, in_len int32 device tensors (n each).  dictionary: bytes of a
         dictionary shared by all slices (host memory; raw content, or zstd's own format -- magic EC30A437 -- with its tables,
         repeat offsets and ID; levels 1, 2, 3 and the negative ones, slices up to 128 KiB; its tables are built once per dictionary and
@@ -351,13 +363,18 @@ class ZstdBatch:
         level: 3 (default); 1 / 2 / a negative level at any size the context holds (with a dictionary: up to 128 KiB); 4 up to 128 KiB and above
         256 KiB; 5 .. 10 (libzstd's greedy / lazy / lazy2 parsers) for slices up to 128 KiB and, on a context created for larger slices, up to
         2 MiB (frames of several blocks, as ZSTD_compress2 writes them) -- at 9 and 10 a slice of 8 bytes .. 16 KiB is another strategy and
-        comes back refused (out_len 0, status bit 4), as do a slice above 2 MiB at levels 5 .. 10 and a level-4 slice between 128 and 256 KiB.
+        comes back refused (out_len 0, status bit 4), as do a slice above 2 MiB at levels 5 .. 10 and, with reference=True, a level-4 slice between 128 and 256 KiB (one-shot frames of that size are served: libzstd's "greedy" row, on
+        the chain kernel of levels 5 .. 10).
         streaming: None = one-shot frames; "data" / "empty" = the frames of slices that arrived through finish = false
         calls, closed by a call with / without data (context created for slices above 128 KiB; levels 1 to 4 and the negative ones at
         any length, 5 .. 10 for streams of 0 .. 2 MiB -- a longer one comes back refused: out_len 0, status bit 4).
         reference: the frames ZstdCompressor(level).transform(bytes) returns -- above 128 KiB the reference's output slices
         make libzstd stage the input in 128 KiB chunks, so they differ from ZSTD_compress2's (the default here) wherever
         the block pre-splitter cuts (no dictionary); up to 128 KiB both are the same.  Levels 5 .. 10: up to 2 MiB, as above.
+        checksum / content_size / dict_id: libzstd's checksumFlag (the low 32 bits of the content's XXH64 behind the last block),
+        contentSizeFlag (False: no content size in the header, a window descriptor instead; decode such frames with out_cap) and dictIDFlag
+        (False: a formatted dictionary's ID is left out).  Given here they hold for this call: the context's flags (set_frame_flags) are put
+        back before it returns; left at their defaults the call writes what the context's flags say.
         Returns (dst, out_off, out_len): frame i = dst[out_off[i] : out_off[i] + out_len[i]]."""
         n = in_len.numel()
         if dst is None:
@@ -366,6 +383,14 @@ class ZstdBatch:
             out_off = torch.arange(n, dtype=torch.int64, device=self.device) * self.out_stride
         if out_len is None:
             out_len = torch.zeros(n, dtype=torch.int32, device=self.device)
+        flags = (self.FRAME_CHECKSUM if checksum else 0) | (0 if content_size else self.FRAME_NO_CONTENT_SIZE) | (0 if dict_id else self.FRAME_NO_DICT_ID)
+        if flags:
+            held = self.frame_flags()
+            self.set_frame_flags(flags)
+            try:                    # (a batch takes the flags when it is queued: they can go back at once)
+                return self.compress(src, in_off, in_len, dst, out_off, out_len, dictionary, level, streaming, reference, check)
+            finally:
+                self.set_frame_flags(held)
         if reference and streaming is None:
             if dictionary is not None:
                 raise ValueError("reference=True is served without a dictionary")

@@ -66,7 +66,7 @@ __global__ __launch_bounds__(256) void k_zstd_lazy_big_init(const u32* in_len, u
 // its own, so that the one-shot kernel keeps its code
 __global__ __launch_bounds__(64, 2) void k_zstd_lazy_big_modes(KLazyBigArgs a) { zstd_lazy_big_body<true>(a); }
 // ... and its init: a stream is taken at every length (an empty one: its nine bytes are written here)
-__global__ __launch_bounds__(256) void k_zstd_lazy_big_init_modes(const u32* in_len, u32 n, KFrameState* fs, KSeqPrev* prev, u8* dst, const u64* out_off, u32* out_len, u32* remaining, u32* status, u32 mode, u32 level)
+__global__ __launch_bounds__(256) void k_zstd_lazy_big_init_modes(const u32* in_len, u32 n, KFrameState* fs, KSeqPrev* prev, u8* dst, const u64* out_off, u32* out_len, u32* remaining, u32* status, u32 mode, u32 level, u32 fflags, const u32* cks)
 {
     u32 const i = blockIdx.x * 256u + threadIdx.x;
     if (i >= n) return;
@@ -75,7 +75,7 @@ __global__ __launch_bounds__(256) void k_zstd_lazy_big_init_modes(const u32* in_
     fs[i] = s;
     if (refused) { out_len[i] = 0; atomicOr(status, (u32)KMP_STATUS_LEVEL_SIZE); }
     else if (s.blockSize) atomicAdd(remaining, 1u);
-    else if (mode != KXF_REFERENCE) out_len[i] = zstd_lazy_big_empty_stream(dst + out_off[i], level);
+    else if (mode != KXF_REFERENCE) out_len[i] = kx_frame_end(dst + out_off[i], zstd_lazy_big_empty_stream(dst + out_off[i], level, fflags), fflags, cks, i);
 }
 // ... of a batch parsed against a formatted dictionary: its tables as the block's predecessor, its ID in the frame header
 __global__ __launch_bounds__(64, 4) void k_zstd_entropy_prior(KEntropyArgs a) { zstd_entropy_body<true>(a); }
@@ -111,8 +111,10 @@ template <int G>
 __global__ __launch_bounds__(64, 3) void k_zstd_big_fast(KBigArgs a) { zstd_big_body<G, true>(a); }
 // first block size, repcodes {1,4,8}, no Huffman table, a fresh window; an empty slice is a header and an empty raw block
 // chunked: the input is taken in chunks of 128 KiB (KFrameArgs.stream != 0); wd: window descriptor byte of a streaming frame, 0 = one-shot
-// level4: slices of the size classes level 4 runs as "greedy" (up to 16 KiB, 128 - 256 KiB; sizes known) are refused: out_len 0, status bit
-__global__ __launch_bounds__(256) void k_zstd_frame_init(const u32* in_len, u32 n, KFrameState* fs, u8* dst, const u64* out_off, u32* out_len, u32* remaining, u32 wd, u32 chunked, u32 level4 = 0, u32* status = nullptr)
+// level4: slices of the size classes level 4 runs as "greedy" (up to 16 KiB, 128 - 256 KiB; sizes known) get no frame here: out_len 0, and the
+// status bit -- except, with level4 == 2, the class above a block, whose frames k_zstd_lazy_big writes behind this batch's chains
+// fflags / cks: the batch's frame flags and checksums (zstd_common.h KXH_*), for the empty slices' frames
+__global__ __launch_bounds__(256) void k_zstd_frame_init(const u32* in_len, u32 n, KFrameState* fs, u8* dst, const u64* out_off, u32* out_len, u32* remaining, u32 wd, u32 chunked, u32 level4, u32* status, u32 fflags, const u32* cks)
 {
     u32 const i = blockIdx.x * 256u + threadIdx.x;
     if (i >= n) return;
@@ -120,7 +122,8 @@ __global__ __launch_bounds__(256) void k_zstd_frame_init(const u32* in_len, u32 
     if (level4 && !wd && !kx_l4_served(len)) {
         s.ipos = 0; s.opos = 0; s.blockSize = 0; s.first = 1; s.rep[0] = 1; s.rep[1] = 4; s.rep[2] = 8; s.hufValid = 0; s.hufSel = 0; s.savings = 0;
         s.lowLimit = 2; s.dictLimit = 2; s.bufPos = 0; s.extBase = 0; s.wflags = 0; s.chunkEnd = 0;
-        fs[i] = s; out_len[i] = 0; if (status) atomicOr(status, (u32)KMP_STATUS_LEVEL_SIZE);
+        // (level4 == 2, the one-shot batch call: the class above a block is not refused, k_zstd_lazy_big writes its frames behind this chain)
+        fs[i] = s; out_len[i] = 0; if (status && !(level4 == 2u && len > KX_BLOCK_MAX)) atomicOr(status, (u32)KMP_STATUS_LEVEL_SIZE);
         return;
     }
     s.ipos = 0; s.opos = 0; s.blockSize = len < KX_BLOCK_MAX ? len : KX_BLOCK_MAX; s.first = 1;
@@ -128,9 +131,28 @@ __global__ __launch_bounds__(256) void k_zstd_frame_init(const u32* in_len, u32 
     s.lowLimit = 2; s.dictLimit = 2; s.bufPos = 0; s.extBase = 0; s.wflags = 0;
     s.chunkEnd = (chunked && len > KX_BLOCK_MAX) ? KX_BLOCK_MAX : len;
     fs[i] = s;
-    if (len == 0) { u8* d = dst + out_off[i]; kx_st32(d, 0xFD2FB528u); d[4] = wd ? 0x00 : 0x20; d[5] = (u8)wd; d[6] = 1; d[7] = 0; d[8] = 0; out_len[i] = 9; }
+    if (len == 0) {
+        u8* d = dst + out_off[i];
+        if (wd) { kx_st32(d, 0xFD2FB528u); d[4] = (u8)((fflags & KXH_CHECKSUM) ? 1u << 2 : 0u); d[5] = (u8)wd; }
+        else kx_write_frame_header(d, 0, kx_window_log_src(0), fflags);      // (six bytes either way: a content size of 0, or the smallest window)
+        d[6] = 1; d[7] = 0; d[8] = 0; out_len[i] = kx_frame_end(d, 9, fflags, cks, i);
+    }
     else atomicAdd(remaining, 1u);
 }
+// level 4's "greedy" class above a block (128 KiB < size <= 256 KiB), behind k_zstd_big: the frame states of those slices for
+// k_zstd_lazy_big at level 4 (kx_lazy_big_params_l4); every other slice's frame is written already and k_zstd_lazy_big passes it over
+__global__ __launch_bounds__(256) void k_zstd_lazy_big_init_l4(const u32* in_len, u32 n, KFrameState* fs, KSeqPrev* prev, u32* remaining)
+{
+    u32 const i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    KFrameState s; bool refused; u32 const len = in_len[i];
+    zstd_lazy_big_init_slice(len, s, prev[i], refused);
+    if (kx_lazy_big_params_l4(len).strat == 0u) s.blockSize = 0;
+    fs[i] = s;
+    if (s.blockSize) atomicAdd(remaining, 1u);
+}
+// XXH64 of every slice of a batch whose frames carry checksums (zstd_seekable.h's body, as the seekable container runs it)
+__global__ __launch_bounds__(256) void k_frame_xxh64(KSeekXxhArgs a) { seekable_xxh64_body(a); }
 __global__ __launch_bounds__(64, 5) void k_zstd_decode(KDecodeArgs a) { zstd_decode_body(a); }
 // the sequence bitstreams decoded ahead of it, one lane per frame (FSE tables in HBM)
 __global__ __launch_bounds__(4 * KXP_FRAMES) void k_zstd_seq_predecode(KPreArgs a) { zstd_seq_predecode_body(a); }
@@ -553,6 +575,7 @@ static int batch_create_body(kmp_batch_ctx* c, int device, uint32_t max_slices, 
         KMP_TRY(c->sweep_rec.alloc((KMP_SWEEP_HEAD + 2 * ns) * sizeof(u32), "hipMalloc(sweep records)"));
         KMP_TRY(c->ev_fork.create(hipEventDisableTiming));
     }
+    KMP_TRY(c->frame_cks.alloc(ns * sizeof(u32), "hipMalloc(frame checksums)"));
     c->knob.match_v2 = KMP_KNOB("KMP_MATCH_V2", 0);                     // 0: zstd_match.h (the default: 4 % faster, both sit on the same memory floor); 1: zstd_match2.h; 2: with a 512-byte window at team width 4
     HIP_TRY(hipStreamSynchronize(c->st2));
     return KMP_OK;
@@ -576,7 +599,7 @@ extern "C" int kmp_batch_memory(kmp_batch_ctx* c, kmp_batch_memory_info* info)
     m.arena = c->arena.bytes;
     if (c->arena) m.arena_used = (size_t)c->nteams * KX_TBL_ENTRIES * sizeof(u32) + ns * c->seq_cap * sizeof(KSeq) + ns * c->lit_cap + ns * sizeof(KSliceMeta) + ns * c->scratch_words * sizeof(u32);
     m.workspace = c->seqs_buf.bytes + c->lits_buf.bytes + c->meta_buf.bytes + c->scratch_buf.bytes + c->tables_buf.bytes
-                + c->team_epoch.bytes + c->counter.bytes + c->len_ok.bytes + c->d_status.bytes + c->sweep_rec.bytes;
+                + c->team_epoch.bytes + c->counter.bytes + c->len_ok.bytes + c->d_status.bytes + c->sweep_rec.bytes + c->frame_cks.bytes;
     m.other_tables = part_bytes(c->flat) + part_bytes(c->t4) + part_bytes(c->chain_t4) + dict_bytes(c) + part_bytes(c->ddict) + part_bytes(c->lz) + part_bytes(c->lzb);
     m.block_chain = c->fstate.bytes + c->hufct.bytes + c->big_tables.bytes + c->remaining.bytes + c->big_counters.bytes;
     m.decode_staging = part_bytes(c->pre_seq) + part_bytes(c->pre_lit);
@@ -586,6 +609,16 @@ extern "C" int kmp_batch_memory(kmp_batch_ctx* c, kmp_batch_memory_info* info)
     return KMP_OK;
 }
 
+/* What the zstd compress batches queued on this context from now on write around their blocks (KMP_FRAME_*): no wait, no device work --
+ * a batch takes the flags as they stand when it is queued (batch_view). */
+extern "C" int kmp_batch_set_frame_flags(kmp_batch_ctx* c, uint32_t flags)
+{
+    if (!c) { g_last_error = "kmp_batch_set_frame_flags: null context"; return KMP_ERR_ARG; }
+    if (flags & ~(uint32_t)(KMP_FRAME_CHECKSUM | KMP_FRAME_NO_CONTENT_SIZE | KMP_FRAME_NO_DICT_ID)) { g_last_error = "kmp_batch_set_frame_flags: unknown flag"; return KMP_ERR_ARG; }
+    c->frame_flags = flags;
+    return KMP_OK;
+}
+extern "C" uint32_t kmp_batch_frame_flags(kmp_batch_ctx* c) { return c ? c->frame_flags : 0u; }
 extern "C" int kmp_batch_set_profiling(kmp_batch_ctx* c, int on) { if (!c) return KMP_ERR_ARG; c->profiling = on; return KMP_OK; }
 // 0 / 1: mean duration of the k_zstd_match / k_zstd_entropy launches of the last timed level-3 batch; 2: decode; 3: DEFLATE.
 // A batch with entropy sweeps beside its parse: 1 is the final sweep alone, the entropy time the step still shows.
@@ -656,7 +689,7 @@ extern "C" int kmp_batch_status(kmp_batch_ctx* c, uint32_t* bits, void* hip_stre
     if (bits) *bits = v;
     if (v & KMP_STATUS_SLICE_TOO_LARGE) { g_last_error = "a slice is larger than the context was created for: its out_len is 0"; return KMP_ERR_CAPACITY; }
     if (v & KMP_STATUS_KERNEL_GUARD) { g_last_error = "a parser's loop guard tripped: the slice's out_len is 0"; return KMP_ERR_KERNEL; }
-    if (v & KMP_STATUS_LEVEL_SIZE) { g_last_error = "the level is not served at a slice's size (levels 9 and 10 up to 16 KiB; level 4 between 128 and 256 KiB; levels 5 .. 10 above 2 MiB): that slice's out_len is 0"; return KMP_ERR_CAPACITY; }
+    if (v & KMP_STATUS_LEVEL_SIZE) { g_last_error = "the level is not served at a slice's size (levels 9 and 10 up to 16 KiB; level 4 up to 16 KiB on a context for larger slices, and between 128 and 256 KiB as a staged frame; levels 5 .. 10 above 2 MiB): that slice's out_len is 0"; return KMP_ERR_CAPACITY; }
     return KMP_OK;
 }
 
@@ -696,7 +729,17 @@ static KBatchView batch_view(kmp_batch_ctx* c, const void* d_src, const uint64_t
 {
     KBatchView v = { (const u8*)d_src, d_in_off, c->len_ok, (u8*)d_dst, d_out_off, d_out_len, n, c->seqs, c->lits, c->meta, c->scratch,
                      kx_work_caps(c->big ? KMP_MAX_SLICE_BYTES : c->max_slice_bytes) };
+    v.fflags = c->frame_flags; v.cks = (v.fflags & KXH_CHECKSUM) ? c->frame_cks.p : nullptr;
     return v;
+}
+// ... and, when its frames carry checksums, the XXH64 pass over its slices, in front of everything that closes a frame (st: where the
+// batch -- or this piece of it -- has begun: the sanitised lengths are there)
+static int frame_checksums(hipStream_t st, KBatchView const& v)
+{
+    if (!(v.fflags & KXH_CHECKSUM) || v.n == 0) return KMP_OK;
+    hipLaunchKernelGGL(k_frame_xxh64, dim3(kx_frame_xxh_blocks(v.n)), dim3(256), 0, st, kx_frame_xxh_args(v));
+    HIP_TRY(hipGetLastError());
+    return KMP_OK;
 }
 static KTeamTables team_tables(kmp_batch_ctx* c) { KTeamTables t = { c->tables, c->team_epoch, c->tseg, c->tseg_n, false }; return t; }
 // the tables of the one-position-per-step parsers (levels 1 / 2, dictionary): the level-3 tables when those are one piece,
@@ -738,6 +781,7 @@ static int zstd_compress_lazy(kmp_batch_ctx* c, const void* d_src, const uint64_
     KMP_TRY(batch_begin(c, st, d_in_len, n, c->max_slice_bytes));          // (first: waits for the context's previous batch, whose workspace this may replace)
     KMP_TRY(lazy_workspace(c, c->max_slice_bytes));
     KBatchView const v = batch_view(c, d_src, d_in_off, n, d_dst, d_out_off, d_out_len);
+    KMP_TRY(frame_checksums(st, v));
     KMP_TRY(lazy_parse(c, st, v, level));
     KEntropyArgs const e = kx_entropy_args(v, kx_entropy_flags_lazy(level));      // literals are gathered by the entropy kernel; the level: it derives each slice's strategy from it
     hipLaunchKernelGGL(k_zstd_entropy, dim3(n), dim3(64), 0, st, e);
@@ -819,6 +863,7 @@ static int zstd_compress_lazy_big(kmp_batch_ctx* c, const void* d_src, const uin
     if (!streaming) KMP_TRY(lazy_workspace(c, KMP_MAX_SLICE_BYTES));
     lazy_big_part const& z = *c->lzb;
     KBatchView const v = batch_view(c, d_src, d_in_off, n, d_dst, d_out_off, d_out_len);
+    KMP_TRY(frame_checksums(st, v));
     if (!streaming) {
         // the one-block slices (the others: empty frames there, replaced below); staged = in place up to 128 KiB
         hipLaunchKernelGGL(k_zstd_lazy_small_len, dim3((n + 255) / 256), dim3(256), 0, st, v.in_len, n, z.small_len.p);
@@ -839,7 +884,7 @@ static int zstd_compress_lazy_big(kmp_batch_ctx* c, const void* d_src, const uin
             hipLaunchKernelGGL(k_zstd_lazy_big_init, dim3((m + 255) / 256), dim3(256), 0, st, pv.in_len, m, c->fstate + first, z.prev.p, pv.out_len, c->remaining.p, c->d_status.p);
             hipLaunchKernelGGL(k_zstd_lazy_big, dim3(m), dim3(64), 0, st, g);
         } else {
-            hipLaunchKernelGGL(k_zstd_lazy_big_init_modes, dim3((m + 255) / 256), dim3(256), 0, st, pv.in_len, m, c->fstate + first, z.prev.p, pv.dst, pv.out_off, pv.out_len, c->remaining.p, c->d_status.p, mode, (u32)level);
+            hipLaunchKernelGGL(k_zstd_lazy_big_init_modes, dim3((m + 255) / 256), dim3(256), 0, st, pv.in_len, m, c->fstate + first, z.prev.p, pv.dst, pv.out_off, pv.out_len, c->remaining.p, c->d_status.p, mode, (u32)level, pv.fflags, pv.cks);
             hipLaunchKernelGGL(k_zstd_lazy_big_modes, dim3(m), dim3(64), 0, st, g);
         }
         HIP_TRY(hipGetLastError());
@@ -880,6 +925,7 @@ extern "C" int kmp_zstd_compress_batch_level(kmp_batch_ctx* c, const void* d_src
     if (chunks == 2) { u32 const pm = c->knob.fast_first_permille; starts[1] = (u32)((u64)n * (pm >= 100 && pm <= 950 ? pm : 500u) / 1000u) & ~63u; if (starts[1] == 0 || starts[1] >= n) chunks = 1, starts[1] = n; }
     bool forked = false;
     KBatchView const v = batch_view(c, d_src, d_in_off, n, d_dst, d_out_off, d_out_len);
+    KMP_TRY(frame_checksums(st, v));
     KTeamTables flat; KMP_TRY(flat_tables(c, &flat));
     for (u32 ci = 0; ci < chunks; ci++) {
         u32 const first = starts[ci], m_n = starts[ci + 1] - first;
@@ -969,6 +1015,7 @@ static int zstd_compress_dict(const char* fn, kmp_batch_ctx* c, const void* d_sr
     KMP_TRY(batch_begin(c, st, d_in_len, n, c->max_slice_bytes));
     HIP_TRY(hipMemsetAsync(c->counter, 0, 4, st));
     KBatchView const v = batch_view(c, d_src, d_in_off, n, d_dst, d_out_off, d_out_len);
+    KMP_TRY(frame_checksums(st, v));
     KTeamTables flat; KMP_TRY(flat_tables(c, &flat));
     u32 const tpw = 64 / (u32)c->G;
     u32 blocks = (n + tpw - 1) / tpw; if (blocks > c->match_blocks) blocks = c->match_blocks;
@@ -984,7 +1031,7 @@ static int zstd_compress_dict(const char* fn, kmp_batch_ctx* c, const void* d_sr
     }
     HIP_TRY(hipGetLastError());
     if (c->profiling) { HIP_TRY(hipEventRecord(c->match[0].end, st)); HIP_TRY(hipEventRecord(c->entropy[0].start, st)); }
-    KEntropyArgs const e = kx_entropy_args(v, eflags, dp.prior);
+    KEntropyArgs const e = kx_entropy_args(v, eflags, dp.prior, dp.size);
     if (dp.prior) hipLaunchKernelGGL(k_zstd_entropy_prior, dim3(n), dim3(64), 0, st, e);
     else hipLaunchKernelGGL(k_zstd_entropy, dim3(n), dim3(64), 0, st, e);
     HIP_TRY(hipGetLastError());
@@ -1007,6 +1054,25 @@ extern "C" int kmp_zstd_compress_batch_dict_level(kmp_batch_ctx* c, const void* 
     return zstd_compress_dict("kmp_zstd_compress_batch_dict_level", c, d_src, d_in_off, d_in_len, n, d_dst, d_out_off, d_out_len, h_dict, dict_size, level, hip_stream);
 }
 
+// Level 4's slices of 128 KiB + 1 .. 256 KiB in a one-shot batch: libzstd parses that size class "greedy" over its row-based match finder
+// (ZSTD_getCParams(4, n)), which is zstd_lazy_big.h's chain with level 4's row.  Runs behind k_zstd_big on the batch's stream: the other
+// slices' frames stand, these slices' states are made anew (k_zstd_lazy_big_init_l4) and their chains walked in pieces of as many slices as the
+// part holds table slots for (5 << 17 bytes each at this row's hashLog).
+static int level4_greedy_class(kmp_batch_ctx* c, hipStream_t st, KBatchView const& v)
+{
+    KMP_TRY(lazy_big_workspace(c, kx_lazy_big_slot_bytes(17u)));
+    lazy_big_part const& z = *c->lzb;
+    for (u32 first = 0; first < v.n; first += z.chunk) {
+        u32 const m = (v.n - first < z.chunk) ? v.n - first : z.chunk;
+        KBatchView const pv = v.sub(first, m);
+        KLazyBigArgs const g = kx_lazy_big_args(pv, c->fstate + first, c->hufct + (size_t)first * 512u, c->remaining, c->d_status, z.tables, z.slot_bytes, z.prev, 4);
+        hipLaunchKernelGGL(k_zstd_lazy_big_init_l4, dim3((m + 255) / 256), dim3(256), 0, st, pv.in_len, m, c->fstate + first, z.prev.p, c->remaining.p);
+        hipLaunchKernelGGL(k_zstd_lazy_big, dim3(m), dim3(64), 0, st, g);
+        HIP_TRY(hipGetLastError());
+    }
+    return KMP_OK;
+}
+
 // Slices above 128 KiB: frames of several blocks.  Every round runs the match kernel and the frame kernel over
 // one block of every unfinished slice; block sizes depend on the bytes already produced (ZSTD_optimalBlockSize),
 // so the rounds are sequential and the host only reads back how many frames are still open.
@@ -1027,16 +1093,22 @@ int zstd_compress_big(kmp_batch_ctx* c, const void* d_src, const uint64_t* d_in_
     HIP_TRY(hipMemsetAsync(c->remaining, 0, 4, st));
     // strategy: 0 level 3 (double-fast), 1 level 1 (fast), 2 level 2 (fast, but double-fast for 128 KiB < size <= 256 KiB when the size is known)
     KBatchView const v = batch_view(c, d_src, d_in_off, n, d_dst, d_out_off, d_out_len);
-    hipLaunchKernelGGL(k_zstd_frame_init, dim3((n + 255) / 256), dim3(256), 0, st, v.in_len, n, c->fstate, v.dst, d_out_off, d_out_len, c->remaining, kx_big_window_byte(stream, strategy), stream != KXF_ONE_SHOT ? 1u : 0u, level4 ? 1u : 0u, c->d_status);
+    KMP_TRY(frame_checksums(st, v));
+#ifdef KMP_ABLATIONS
+    bool const chains = strategy || c->knob.big_rounds == 0;
+#else
+    bool const chains = true;
+#endif
+    // level 4, sizes known: the "greedy" class above a block (128 - 256 KiB) goes through k_zstd_lazy_big behind the chains of the others (one-shot
+    // frames on the product path); staged frames of that class and the class up to 16 KiB stay refused here
+    bool const l4_greedy = level4 && stream == KXF_ONE_SHOT && chains;
+    hipLaunchKernelGGL(k_zstd_frame_init, dim3((n + 255) / 256), dim3(256), 0, st, v.in_len, n, c->fstate, v.dst, d_out_off, d_out_len, c->remaining, kx_big_window_byte(stream, strategy), stream != KXF_ONE_SHOT ? 1u : 0u, level4 ? (l4_greedy ? 2u : 1u) : 0u, c->d_status, v.fflags, v.cks);
     HIP_TRY(hipGetLastError());
     KMatchArgs const m = kx_match_args_blk(v, team_tables(c), c->counter, streaming, c->max_slice_bytes >= KX_BLK_WIDE_FROM, c->fstate, level4 ? c->chain_t4->tables.p : c->big_tables.p, level4);
     // (a negative level: the level-1 machinery (window 2^19) on row 0 of the tables, a step of 1 - level, raw literals)
     KBigLevel const lv = { strategy, fast_step0, level4 };
     KFrameArgs const e = kx_frame_args(v, c->fstate, c->hufct, c->remaining, c->d_status, stream, lv, tail_direct);
-#ifdef KMP_ABLATIONS
-    if (strategy || c->knob.big_rounds == 0)
-#endif
-    {
+    if (chains) {
         // one wave per slice walks its chain of blocks
         // few slices: one per wave (most waves); many: up to 64 / G per wave so that all of them are in flight
         // lanes per slice: every slice of the batch should be in flight (its block chain is serial), and a parse team
@@ -1064,6 +1136,7 @@ int zstd_compress_big(kmp_batch_ctx* c, const void* d_src, const uint64_t* d_in_
         if (strategy) by_team_width(bigG, [&](auto w) { hipLaunchKernelGGL(k_zstd_big_fast<decltype(w)::value>, dim3(grid), dim3(64), 0, st, g); });
         else by_team_width(bigG, [&](auto w) { hipLaunchKernelGGL(k_zstd_big<decltype(w)::value>, dim3(grid), dim3(64), 0, st, g); });
         HIP_TRY(hipGetLastError());
+        if (l4_greedy) KMP_TRY(level4_greedy_class(c, st, v));
         c->last_rounds = 0; c->last_chunks = 1; c->zstd_timed = 0;
         return batch_end(c, st, d_in_len, n, c->max_slice_bytes, d_out_len, nullptr);
     }
@@ -1214,6 +1287,7 @@ static int zstd_compress_dfast(kmp_batch_ctx* c, const void* d_src, const uint64
     KSweepRecords const rec = { c->sweep_rec + KMP_SWEEP_HEAD, c->sweep_rec + KMP_SWEEP_HEAD + n, c->sweep_rec };
     c->last_sweeps = 0;
     KBatchView const v = batch_view(c, d_src, d_in_off, n, d_dst, d_out_off, d_out_len);
+    KMP_TRY(frame_checksums(st, v));
     KTeamTables const tables = l4 ? kx_one_piece(c->t4->tables, c->t4->epochs, true) : team_tables(c);
     for (u32 ci = 0; ci < chunks; ci++) {
         u32 const first = starts[ci], m_n = starts[ci + 1] - first;
@@ -1330,6 +1404,7 @@ int piece_enqueue(kmp_batch_ctx* c, u32 p, u32 pieces, const void* d_src, const 
     hipLaunchKernelGGL(k_len_guard, dim3((m_n + 255) / 256), dim3(256), 0, st, d_in_len + first, m_n, c->max_slice_bytes, c->len_ok + first, c->d_status);
     HIP_TRY(hipMemsetAsync(c->counter + p, 0, 4, st));
     KBatchView const v = batch_view(c, d_src, d_in_off, n, d_dst, d_out_off, d_out_len).sub(first, m_n);
+    KMP_TRY(frame_checksums(st, v));
     KMatchArgs const m = kx_match_args(v, team_tables(c), c->counter + p, c->knob.match_flags, p * blocks_per_piece);
     u32 blocks = (m_n + tpw - 1) / tpw; if (blocks > blocks_per_piece) blocks = blocks_per_piece;
     by_team_width(c->G, [&](auto w) { hipLaunchKernelGGL(k_zstd_match<decltype(w)::value>, dim3(blocks), dim3(64), 0, st, m); });

@@ -60,7 +60,8 @@ template <class F> static void host_parallel(u32 threads, u32 count, F const& fn
     for (auto& t : th) t.join();
 }
 
-struct host_job { const u8* in; u32 len; u8* out; u32 out_cap; u32 out_len; u32 status; std::vector<u8>* out_vec; bool done; int batch_rc; };
+// fflags: the frame flags (KMP_FRAME_*) the job's frame is written with -- the coalescer's compress jobs; the host batch calls leave 0
+struct host_job { const u8* in; u32 len; u8* out; u32 out_cap; u32 out_len; u32 status; std::vector<u8>* out_vec; bool done; int batch_rc; u32 fflags = 0; };
 
 struct host_engine {
     int device = 0; u32 cap_slices = 0; u32 slice_cap = 0; size_t stride = 0;
@@ -128,10 +129,16 @@ static host_engine* host_engine_get(int device, int slot = 0)
 // Compresses jobs[0 .. n) (n <= cap_slices, every len <= 128 KiB) at any level the batch call serves: one H2D copy, the device
 // batch, the dense packing, two D2H copies.  A frame goes to job.out (out_cap bytes; status 70 = too small) or to job.out_vec;
 // status 1 = the device refused the slice (level 4's greedy size classes: out_len 0, the call returns KMP_ERR_CAPACITY).
-static int host_engine_compress(host_engine* e, host_job* jobs, u32 n, int level, bool* ran = nullptr)
+// fflags: the frame flags of the whole batch (the engine's context carries them for this batch alone).
+static int host_engine_compress(host_engine* e, host_job* jobs, u32 n, int level, bool* ran = nullptr, u32 fflags = 0)
 {
     if (ran) *ran = false;
     std::lock_guard<std::mutex> g(e->run_mutex);
+    struct flags_for_batch {
+        kmp_batch_ctx* c;
+        flags_for_batch(kmp_batch_ctx* ctx, u32 f) : c(ctx) { c->frame_flags = f; }
+        ~flags_for_batch() { c->frame_flags = 0; }
+    } const held(e->batch.get(), fflags);
     device_guard const on(e->device);
     size_t pos = 0;
     for (u32 i = 0; i < n; i++) {
@@ -580,7 +587,9 @@ extern "C" int kmp_host_engines_release(int device)
 // ---- the coalescer of kmp_zstd_compress_stream ---------------------------------------------------------------------
 // A closing call of the plain kind queues its slice and waits.  The first waiter leads: it gives others
 // KMP_COALESCE_US (default 150) microseconds to join -- or until KMP_COALESCE_MAX (default 256) slices wait --, runs
-// them as one batch, hands the frames out and passes the lead on if more have queued meanwhile.  The window is only spent
+// them as one batch, hands the frames out and passes the lead on if more have queued meanwhile.  A batch is written with one set of
+// frame flags: the leader takes the jobs whose flags are those of the first one waiting, the others stay queued for the next batch (their
+// order kept), as contexts of another level stay out altogether.  The window is only spent
 // when contexts have been seen closing at the same time lately (a lone caller does not pay it); 64 concurrent contexts share
 // one launch of each kernel instead of queueing 64 batches of one.
 struct coalescer {
@@ -627,16 +636,17 @@ static int coalesced_run(int device, int decode, host_job& job)
             c->leading = true;
             u32 const cap = c->max_batch < e->cap_slices ? c->max_batch : e->cap_slices;
             if (c->crowd) { c->crowd--; c->cv.wait_for(lk, std::chrono::microseconds(c->window_us), [&] { return c->queue.size() >= cap; }); }
-            std::vector<host_job*> mine;
-            u32 const take = c->queue.size() < cap ? (u32)c->queue.size() : cap;
-            mine.assign(c->queue.begin(), c->queue.begin() + take);
-            c->queue.erase(c->queue.begin(), c->queue.begin() + take);
+            std::vector<host_job*> mine, rest;
+            u32 const fflags = c->queue.front()->fflags;                  // (my own job is queued: the queue is not empty)
+            for (host_job* j : c->queue) (j->fflags == fflags && mine.size() < cap ? mine : rest).push_back(j);
+            c->queue.swap(rest);
+            u32 const take = (u32)mine.size();
             if (take > 1) c->crowd = 64;
             lk.unlock();
             std::vector<host_job> batch(take);
             for (u32 i = 0; i < take; i++) batch[i] = *mine[i];
             bool ran = false;
-            int const rc = decode ? host_engine_decompress(e, batch.data(), take) : host_engine_compress(e, batch.data(), take, 3, &ran);
+            int const rc = decode ? host_engine_decompress(e, batch.data(), take) : host_engine_compress(e, batch.data(), take, 3, &ran, fflags);
             // per-entry outcomes (a frame that does not decode, a small output region) are the entries' own: the batch itself ran
             bool const batch_ran = decode ? rc == KMP_OK : ran;
             lk.lock();
@@ -653,10 +663,11 @@ static int coalesced_run(int device, int decode, host_job& job)
         c->cv.wait(lk);
     }
 }
-// the frame of `in` (len <= 128 KiB, level 3, no dictionary) into *out; KMP_OK = the frame is there, anything else: compress alone
-static int coalesced_compress(int device, const u8* in, u32 len, std::vector<u8>* out)
+// the frame of `in` (len <= 128 KiB, level 3, no dictionary) under the frame flags fflags into *out; KMP_OK = the frame is there, anything
+// else: compress alone
+static int coalesced_compress(int device, const u8* in, u32 len, std::vector<u8>* out, u32 fflags)
 {
-    host_job job; job.in = in; job.len = len; job.out = nullptr; job.out_cap = 0; job.out_vec = out;
+    host_job job; job.in = in; job.len = len; job.out = nullptr; job.out_cap = 0; job.out_vec = out; job.fflags = fflags;
     int const rc = coalesced_run(device, 0, job);
     if (rc != KMP_OK) return rc;
     return (job.status || job.out_len == 0) ? KMP_ERR_KERNEL : KMP_OK;

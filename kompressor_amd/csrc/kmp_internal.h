@@ -169,6 +169,9 @@ struct kmp_batch_ctx {
     u32* tseg[4] = { nullptr, nullptr, nullptr, nullptr }; u32 tseg_n = 0;       // the team tables in four pieces spread over the arena (or tseg_n == 1: tables alone)
     dev_buf<u32> team_epoch, counter;
     dev_buf<u32> len_ok, d_status;                // sanitised slice lengths of the running batch; status word (KMP_STATUS_*)
+    // kmp_batch_set_frame_flags: what the zstd compress batches queued from now on write around their blocks (KMP_FRAME_*); frame_cks: the
+    // running batch's checksums, one word per slice (the XXH64 pass of a batch with KMP_FRAME_CHECKSUM fills it)
+    u32 frame_flags = 0; dev_buf<u32> frame_cks;
     u32 table_layout = 0;                         // which of the arena's layouts holds the table pieces (1 .. 8; 0: no arena)
     float place_ms = 0; u32 place_tried = 0;      // the team tables' placement: probe time of the region kept, candidates tried
     float table_reads_per_s = 0, table_pairs_per_s = 0;     // random loads / load + store pairs per second over this context's team tables (k_table_probe at creation; 0 = not measured)

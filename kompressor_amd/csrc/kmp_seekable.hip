@@ -77,7 +77,11 @@ extern "C" int kmp_zstd_seekable_compress(kmp_batch_ctx* c, const void* d_src, s
             KSeekXxhArgs const x = { (const u8*)d_src, in_off, in_len, n, cks, nullptr, nullptr };
             KMP_TRY(launch_xxh64(st, x));
         }
-        KMP_TRY(kmp_zstd_compress_batch_level(c, d_src, in_off, in_len, n, s + l.frames, out_off, out_len, level, hip_stream));
+        // (the container's frames stay as the format specifies them, whatever kmp_batch_set_frame_flags has left on the context)
+        u32 const held = c->frame_flags; c->frame_flags = 0;
+        int const rc = kmp_zstd_compress_batch_level(c, d_src, in_off, in_len, n, s + l.frames, out_off, out_len, level, hip_stream);
+        c->frame_flags = held;
+        KMP_TRY(rc);
         KMP_TRY(kmp_compact_batch(c, s + l.frames, out_off, out_len, n, d_dst, dense_off, hip_stream));
     }
     KSeekTableArgs const t = { (u8*)d_dst, dense_off, out_len, in_len, cks, n, flags & KMP_SEEKABLE_CHECKSUMS, c->d_status, d_result };

@@ -101,6 +101,7 @@ struct kmp_zstd_cctx {
     std::vector<u8> dict;                       // raw-content dictionary (ZSTD_CCtx_loadDictionary keeps a copy too)
     size_t fed_continue = 0;                    // bytes that arrived with ZSTD_e_continue: > 0 makes it a streaming frame
     int end_was_empty = 0;                      // the closing calls brought no data
+    u32 fflags = 0;                             // KMP_FRAME_*: ZSTD_c_contentSizeFlag = 0 / ZSTD_c_checksumFlag = 1 / ZSTD_c_dictIDFlag = 0
 };
 
 extern "C" kmp_zstd_cctx* kmp_zstd_create_cctx(void) { return new (std::nothrow) kmp_zstd_cctx(); }
@@ -108,6 +109,16 @@ extern "C" size_t kmp_zstd_free_cctx(kmp_zstd_cctx* c) { delete c; return 0; }
 extern "C" size_t kmp_zstd_cctx_set_parameter(kmp_zstd_cctx* c, int param, int value)
 {
     if (!c) return KERRC(ZE_GENERIC);
+    if (param == KMP_ZSTD_c_contentSizeFlag || param == KMP_ZSTD_c_checksumFlag || param == KMP_ZSTD_c_dictIDFlag) {
+        // the three parameters that shape a frame's header and trailer: the batch the frame comes from is queued with them
+        // (kmp_batch_set_frame_flags).  Returns the value set, as libzstd does
+        if (c->stage != 0 || !c->in.empty()) return KERRC(ZE_stage_wrong);
+        if (value != 0 && value != 1) return KERRC(ZE_parameter_outOfBound);
+        u32 const bit = param == KMP_ZSTD_c_checksumFlag ? KMP_FRAME_CHECKSUM : param == KMP_ZSTD_c_contentSizeFlag ? KMP_FRAME_NO_CONTENT_SIZE : KMP_FRAME_NO_DICT_ID;
+        bool const on = param == KMP_ZSTD_c_checksumFlag ? value == 1 : value == 0;          // (the other two are on by default: the bit says "off")
+        c->fflags = on ? c->fflags | bit : c->fflags & ~bit;
+        return (size_t)value;
+    }
     if (param != KMP_ZSTD_c_compressionLevel) return KERRC(ZE_parameter_unsupported);
     if (c->stage != 0 || !c->in.empty()) return KERRC(ZE_stage_wrong);
     if (value == 0) value = 3;
@@ -162,7 +173,7 @@ static size_t run_single_compress(kmp_zstd_cctx* c, size_t first_room, size_t en
     if (!streaming && c->level == 3 && c->dict.empty() && n <= KMP_MAX_SLICE_BYTES && coalesce_enabled()) {
         int dev = 0;
         if (c->dev.batch) dev = c->dev.batch->device; else if (hipGetDevice(&dev) != hipSuccess) return KERRC(ZE_GENERIC);
-        int const rc = coalesced_compress(dev, c->in.data(), (u32)n, &c->out);
+        int const rc = coalesced_compress(dev, c->in.data(), (u32)n, &c->out, c->fflags);
         if (rc == KMP_OK) return 0;
         (void)hipGetLastError();                    // fall through: compress alone
     }
@@ -170,6 +181,7 @@ static size_t run_single_compress(kmp_zstd_cctx* c, size_t first_room, size_t en
     if (!stream_dev_select(c->dev)) return KERRC(ZE_GENERIC);
     { size_t const e = stream_dev_init(c->dev, streaming && n <= KMP_MAX_SLICE_BYTES ? KMP_MAX_SLICE_BYTES + 1 : n); if (e) return e; }
     stream_dev& s = c->dev;
+    if (kmp_batch_set_frame_flags(s.batch.get(), c->fflags) != KMP_OK) return KERRC(ZE_GENERIC);       // (the context is this stream's own)
     u64 offs[2] = { 0, 0 }; u32 len = (u32)n, olen = 0;
     if (n && hipMemcpy(s.d_in, c->in.data(), n, hipMemcpyHostToDevice) != hipSuccess) return KERRC(ZE_GENERIC);
     if (hipMemcpy(s.d_off, offs, sizeof(offs), hipMemcpyHostToDevice) != hipSuccess) return KERRC(ZE_GENERIC);

@@ -138,25 +138,45 @@ KX_DEV bool kx_in_class(u32 cls, u32 n) { return cls == KXC_ALL || ((n > 131072u
 // "repeat" sequence tables) --, the repeat offsets a frame starts with, and the ID a frame's header may name.  Host: zstd_cdict_host.h.
 struct KDictDPrior { u8 weights[256]; u32 nw, hufLog; short norm[3][64]; u32 log[3], max[3]; u32 rep[3]; u32 dictID; };       // [0] LL, [1] OF, [2] ML
 
-KX_DEV u32 kx_frame_header_size(u32 n, u32 windowLog = 21)
+// The frame flags of a batch (KMP_FRAME_* of the public header, kmp_batch_set_frame_flags), as every frame writer's launch arguments
+// carry them: ZSTD_c_checksumFlag = 1 (descriptor bit 2, and the low 32 bits of the content's XXH64 behind the last block: the batch's
+// XXH64 pass has left them in KEntropyArgs / KFrameArgs.cks), ZSTD_c_contentSizeFlag = 0 (no single segment, no Frame_Content_Size: a
+// window descriptor instead), ZSTD_c_dictIDFlag = 0 (no Dictionary_ID field)
+enum : u32 { KXH_CHECKSUM = 1u, KXH_NO_CONTENT_SIZE = 2u, KXH_NO_DICT_ID = 4u };
+// the window log a frame without content size names when libzstd knew that t bytes (the source, and a copied dictionary) would come:
+// ZSTD_adjustCParams_internal cuts every served row's window down to them, ZSTD_WINDOWLOG_ABSOLUTEMIN holds it up
+KX_DEV u32 kx_window_log_src(u32 t) { u32 const l = (t < 64) ? 6 : kx_hb32(t - 1) + 1; return l < 10 ? 10 : l; }
+
+// windowLog: the level's window for a frame with its content size (single segment while it covers the content), the window the slice is
+// parsed with for one without (fflags & KXH_NO_CONTENT_SIZE)
+KX_DEV u32 kx_frame_header_size(u32 n, u32 windowLog = 21, u32 fflags = 0)
 {
+    if (fflags & KXH_NO_CONTENT_SIZE) return 6;
     // magic(4) + FHD(1) + FCS; single segment while the window (2 MiB at level 3; 512 KiB / 1 MiB at the "fast" levels) covers the
     // content, else a window descriptor byte as well
     return 5 + ((n < 256) ? 1 : (n < 65536 + 256) ? 2 : 4) + (n > (1u << windowLog) ? 1u : 0u);
 }
-// frame header of a one-shot frame (content size known): returns its size
-KX_DEV u32 kx_write_frame_header(u8* dst, u32 n, u32 windowLog = 21)
+// frame header of a one-shot frame (content size known unless the flags leave it out): returns its size
+KX_DEV u32 kx_write_frame_header(u8* dst, u32 n, u32 windowLog = 21, u32 fflags = 0)
 {
+    u32 const cks = (fflags & KXH_CHECKSUM) ? 1u << 2 : 0u;
+    kx_st32(dst, 0xFD2FB528u);
+    if (fflags & KXH_NO_CONTENT_SIZE) { dst[4] = (u8)cks; dst[5] = (u8)((windowLog - 10) << 3); return 6; }
     u32 const fcsCode = (n >= 256) + (n >= 65536 + 256);
     bool const single = n <= (1u << windowLog);
-    kx_st32(dst, 0xFD2FB528u);
-    dst[4] = (u8)((single ? 1u << 5 : 0u) + (fcsCode << 6));
+    dst[4] = (u8)((single ? 1u << 5 : 0u) + (fcsCode << 6) + cks);
     u32 p = 5;
     if (!single) dst[p++] = (u8)((windowLog - 10) << 3);
     if (fcsCode == 0) dst[p++] = (u8)n;
     else if (fcsCode == 1) { kx_st16(dst + p, n - 256); p += 2; }
     else { kx_st32(dst + p, n); p += 4; }
     return p;
+}
+// a frame's last block ends at dst + end: the checksum behind it when the flags ask for one; returns the frame's size (one lane)
+KX_DEV u32 kx_frame_end(u8* dst, u32 end, u32 fflags, const u32* cks, u32 slice)
+{
+    if (fflags & KXH_CHECKSUM) { kx_st32(dst + end, cks[slice]); end += 4; }
+    return end;
 }
 
 // 64-bit multiplicative hashes, top bits. Written with 32-bit pieces: only the

@@ -30,6 +30,9 @@ struct KEntropyArgs {
     u32 flags;                               // KXE_* below
     // KXE_SWEEP: the parse's completion records (KMatchArgs.done), which slices a sweep has coded, and (optional) where a sweep counts them
     const u32* done = nullptr; u32* coded = nullptr; u32* swept = nullptr;
+    // the batch's frame flags (KXH_*, zstd_common.h); KXH_CHECKSUM: the slices' checksums, from the batch's XXH64 pass; dict_total: the
+    // whole dictionary's size (a frame without content size names the window libzstd derives from the slice and a copied dictionary)
+    u32 fflags = 0; const u32* cks = nullptr; u32 dict_total = 0;
 };
 // KEntropyArgs.flags (the low eleven bits travel on to kzstd_sequences as its xflags)
 enum : u32 {
@@ -1180,23 +1183,33 @@ KX_DEV void zstd_entropy_slice(const KEntropyArgs& a, KEntropyLds& lds, u32 slic
     const u8* const src = a.src + a.in_off[slice];
     u32 const n = a.in_len[slice];
     u8* const dst = a.dst + a.out_off[slice];
-    u32 const dictID = PRIOR ? a.prior->dictID : 0u;
+    u32 const dictID = (PRIOR && !(a.fflags & KXH_NO_DICT_ID)) ? a.prior->dictID : 0u;
     u32 const idCode = PRIOR ? (dictID > 0u) + (dictID >= 256u) + (dictID >= 65536u) : 0u, idBytes = idCode == 3u ? 4u : idCode;
-    u32 const fh = kx_frame_header_size(n) + idBytes;
+    u32 const fh = kx_frame_header_size(n, 21, a.fflags) + idBytes;
     if (lane == 0) {
-        u32 const fcsCode = (n >= 256) + (n >= 65536 + 256);
+        u32 const cksBit = (a.fflags & KXH_CHECKSUM) ? 1u << 2 : 0u;
         kx_st32(dst, 0xFD2FB528u);
-        dst[4] = (u8)(idCode + (1u << 5) + (fcsCode << 6));
         u8* p = dst + 5;
+        if (a.fflags & KXH_NO_CONTENT_SIZE) {
+            // the window of the slice's row cut down to the source (every served level's row covers it up to 128 KiB); with a dictionary
+            // that the parse copies (above the strategy's attach cut-off: zstd_match_dict.h, zstd_match_fast_dict.h) to source + dictionary
+            bool const copied = a.dict_total != 0u && n > ((a.flags & KXE_STRATEGY_FAST) ? 8192u : 16384u);
+            dst[4] = (u8)(idCode + cksBit);
+            *p++ = (u8)((kx_window_log_src(n + (copied ? a.dict_total : 0u)) - 10u) << 3);
+        }
         if (idCode == 1) p[0] = (u8)dictID; else if (idCode == 2) kx_st16(p, dictID); else if (idCode == 3) kx_st32(p, dictID);
         p += idBytes;
-        if (fcsCode == 0) p[0] = (u8)n;
-        else if (fcsCode == 1) kx_st16(p, n - 256);
-        else kx_st32(p, n);
+        if (!(a.fflags & KXH_NO_CONTENT_SIZE)) {
+            u32 const fcsCode = (n >= 256) + (n >= 65536 + 256);
+            dst[4] = (u8)(idCode + cksBit + (1u << 5) + (fcsCode << 6));
+            if (fcsCode == 0) p[0] = (u8)n;
+            else if (fcsCode == 1) kx_st16(p, n - 256);
+            else kx_st32(p, n);
+        }
     }
     u8* const bh = dst + fh; u8* const body = bh + 3;
     if (n == 0) {
-        if (lane == 0) { bh[0] = 1; bh[1] = 0; bh[2] = 0; a.out_len[slice] = fh + 3; }
+        if (lane == 0) { bh[0] = 1; bh[1] = 0; bh[2] = 0; a.out_len[slice] = kx_frame_end(dst, fh + 3, a.fflags, a.cks, slice); }
         return;
     }
     u32 cSize = 0;
@@ -1227,10 +1240,10 @@ KX_DEV void zstd_entropy_slice(const KEntropyArgs& a, KEntropyLds& lds, u32 slic
     kx_sync();
     if (cSize == 0) {
         kx_wave_copy(body, src, n, lane);
-        if (lane == 0) { u32 const h = 1u + (0u << 1) + (n << 3); bh[0] = (u8)h; bh[1] = (u8)(h >> 8); bh[2] = (u8)(h >> 16); a.out_len[slice] = fh + 3 + n; }
+        if (lane == 0) { u32 const h = 1u + (0u << 1) + (n << 3); bh[0] = (u8)h; bh[1] = (u8)(h >> 8); bh[2] = (u8)(h >> 16); a.out_len[slice] = kx_frame_end(dst, fh + 3 + n, a.fflags, a.cks, slice); }
     } else if (lane == 0) {
         u32 const h = 1u + (2u << 1) + (cSize << 3); bh[0] = (u8)h; bh[1] = (u8)(h >> 8); bh[2] = (u8)(h >> 16);
-        a.out_len[slice] = fh + 3 + cSize;
+        a.out_len[slice] = kx_frame_end(dst, fh + 3 + cSize, a.fflags, a.cks, slice);
     }
 }
 
@@ -1260,6 +1273,7 @@ struct KFrameArgs {
                                              // their bound in its output slice (compressed in place as one chunk); else 0
     u32 out_chunk;                           // KXF_REFERENCE: size of the driver's output slices; 0 = the reference's max(8192, n / 10)
     u32* status_word = nullptr;              // the context's status word: bit 1 (KMP_STATUS_KERNEL_GUARD) when a block's parser tripped its loop guard
+    u32 fflags = 0; const u32* cks = nullptr;  // the batch's frame flags (KXH_*, zstd_common.h) and, with KXH_CHECKSUM, the slices' checksums
 };
 enum : u32 { KXF_ONE_SHOT = 0u, KXF_STREAM = 1u, KXF_STREAM_EMPTY_END = 2u, KXF_REFERENCE = 3u };      // KFrameArgs.stream
 
@@ -1425,14 +1439,18 @@ KX_DEV void zstd_frame_block(const KFrameArgs& a, KEntropyLds& lds, u32 slice, i
     // header carries a window descriptor instead of the single-segment flag
     u32 const fastLevel = a.fast_step0 ? 0u : a.level2 ? 2u : 1u;
     u32 const wlogKnown = LAZY ? lz->windowLog : a.strategy ? kx_window_log_fast(fastLevel, n, false) : 21u;
+    // the window the slice is parsed with: beyond it libzstd's staging buffer wraps and the window slides (the "fast" levels too, since round 4);
+    // a one-shot frame without content size names it
+    u32 const windowLog = LAZY ? lz->windowLog : a.strategy ? kx_window_log_fast(fastLevel, n, streaming) : (streaming ? 21u : a.level2 ? 18u : kx_params_l3(n).windowLog);
+    u32 const wlogHeader = (a.fflags & KXH_NO_CONTENT_SIZE) ? windowLog : wlogKnown;
     if (fs.ipos == 0 && streaming) {
         // streaming frame header: no content size, window descriptor for 2^21 (the fast levels: 2^19 / 2^20; levels 5 .. 10: their row's)
-        if (lane == 0) { kx_st32(dst, 0xFD2FB528u); dst[4] = 0; dst[5] = (u8)(((LAZY_MODES ? lz->windowLog : a.strategy ? (a.level2 ? 20u : 19u) : 21u) - 10u) << 3); }
+        if (lane == 0) { kx_st32(dst, 0xFD2FB528u); dst[4] = (u8)((a.fflags & KXH_CHECKSUM) ? 1u << 2 : 0u); dst[5] = (u8)(((LAZY_MODES ? lz->windowLog : a.strategy ? (a.level2 ? 20u : 19u) : 21u) - 10u) << 3); }
         fs.opos = 6;
     } else if (fs.ipos == 0) {
         // frame header: content size; single segment while the window covers the slice
-        if (lane == 0) kx_write_frame_header(dst, n, wlogKnown);
-        fs.opos = kx_frame_header_size(n, wlogKnown);
+        if (lane == 0) kx_write_frame_header(dst, n, wlogHeader, a.fflags);
+        fs.opos = kx_frame_header_size(n, wlogHeader, a.fflags);
     }
     u32 const bs = fs.blockSize;
     const u8* const bsrc = src + fs.ipos;
@@ -1499,10 +1517,8 @@ KX_DEV void zstd_frame_block(const KFrameArgs& a, KEntropyLds& lds, u32 slice, i
     // ZSTD_optimalBlockSize for the next block (staged input is compressed in chunks of 128 KiB; the frame header counts
     // as produced from the second chunk on)
     u32 next = 0;
-    if (a.stream && fs.ipos == KX_BLOCK_MAX) fs.savings -= streaming ? 6 : (int)kx_frame_header_size(n, wlogKnown);
+    if (a.stream && fs.ipos == KX_BLOCK_MAX) fs.savings -= streaming ? 6 : (int)kx_frame_header_size(n, wlogHeader, a.fflags);
     if (fs.ipos < n) {
-        // the window of the level: beyond it libzstd's staging buffer wraps and the window slides (the "fast" levels too, since round 4)
-        u32 const windowLog = LAZY ? lz->windowLog : a.strategy ? kx_window_log_fast(fastLevel, n, streaming) : (streaming ? 21u : a.level2 ? 18u : kx_params_l3(n).windowLog);
         u32 const remaining = kx_frame_window_step(fs, n, a.stream, windowLog, a.tail_direct, a.out_chunk);
         if (remaining < KX_BLOCK_MAX) next = remaining;
         else if (fs.savings < 3) next = KX_BLOCK_MAX;
@@ -1513,7 +1529,7 @@ KX_DEV void zstd_frame_block(const KFrameArgs& a, KEntropyLds& lds, u32 slice, i
     if (lane == 0) {
         if (next == 0 && emptyEnd) { u8* const e = dst + fs.opos; e[0] = 1; e[1] = 0; e[2] = 0; fs.opos += 3; }
         a.fstate[slice] = fs;
-        if (next == 0) { a.out_len[slice] = fs.opos; kx_atomic_add(a.remaining, 0xFFFFFFFFu); }
+        if (next == 0) { a.out_len[slice] = kx_frame_end(dst, fs.opos, a.fflags, a.cks, slice); kx_atomic_add(a.remaining, 0xFFFFFFFFu); }
     }
 }
 

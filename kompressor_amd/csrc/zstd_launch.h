@@ -7,6 +7,7 @@
 #include "zstd_match_fast_dict.h"
 #include "zstd_lazy.h"
 #include "zstd_lazy_big.h"
+#include "zstd_seekable.h"          // (the XXH64 body of a batch whose frames carry checksums)
 #include <type_traits>
 
 // The parsers are templates on their team width (lanes per slice): f(std::integral_constant<int, G>()) for G = 2 .. 64 (else 64)
@@ -36,12 +37,16 @@ inline KWorkCaps kx_work_caps(u32 block_cap)
 struct KBatchView {
     const u8* src; const u64* in_off; const u32* in_len; u8* dst; const u64* out_off; u32* out_len; u32 n;
     KSeq* seqs; u8* lits; KSliceMeta* meta; u32* scratch; KWorkCaps cap;
+    // the frame flags the batch was queued with (KXH_*: every argument struct below that writes frames takes them from here) and, with
+    // KXH_CHECKSUM, one word per slice that the batch's XXH64 pass fills (kx_frame_xxh_args) before any frame is closed
+    u32 fflags = 0; u32* cks = nullptr;
     // the slices [first, first + count): the one place where the per-slice strides are applied (src and dst are addressed by the offsets)
     KBatchView sub(u32 first, u32 count) const
     {
         KBatchView v = *this;
         v.in_off += first; v.in_len += first; v.out_off += first; v.out_len += first; v.n = count;
         v.seqs += (size_t)first * cap.seq_cap; v.lits += (size_t)first * cap.lit_cap; v.meta += first; v.scratch += (size_t)first * cap.scratch_words;
+        if (v.cks) v.cks += first;
         return v;
     }
 };
@@ -115,15 +120,28 @@ inline KLazyArgs kx_lazy_args(KBatchView const& v, KLazyRec* rec, u32* wr, u32 p
 inline u32 kx_entropy_flags_dfast(u32 match_flags, bool level4) { return ((match_flags & KXM_NO_LITS) ? KXE_GATHER_LITS : 0u) | (level4 ? 4u << KXE_LEVEL_SHIFT : 0u); }
 inline u32 kx_entropy_flags_fast(bool negative) { return KXE_GATHER_LITS | KXE_STRATEGY_FAST | (negative ? KXE_RAW_LITS : 0u); }
 inline u32 kx_entropy_flags_lazy(int level) { return KXE_GATHER_LITS | ((u32)level << KXE_LEVEL_SHIFT); }
-inline KEntropyArgs kx_entropy_args(KBatchView const& v, u32 flags, const KDictPrior* prior = nullptr)
+// dict_total: the whole dictionary's bytes when the batch was parsed against one (raw or formatted), else 0
+inline KEntropyArgs kx_entropy_args(KBatchView const& v, u32 flags, const KDictPrior* prior = nullptr, u32 dict_total = 0)
 {
     KEntropyArgs e;
     e.src = v.src; e.in_off = v.in_off; e.in_len = v.in_len; e.n_slices = v.n;
     e.seqs = v.seqs; e.seq_cap = v.cap.seq_cap; e.lits = v.lits; e.lit_cap = v.cap.lit_cap; e.meta = v.meta;
     e.scratch = v.scratch; e.scratch_words = v.cap.scratch_words;
     e.dst = v.dst; e.out_off = v.out_off; e.out_len = v.out_len; e.prior = prior; e.flags = flags;
+    e.fflags = v.fflags; e.cks = v.cks; e.dict_total = dict_total;
     return e;
 }
+
+// The XXH64 pass of a batch with KXH_CHECKSUM, in front of its first frame writer: zstd_seekable.h's quad-per-piece body over the view's
+// slices, the low 32 bits (seed 0) of slice i to v.cks[i].  A quad walks its slice alone, so one slice of 1 GiB takes as long as a
+// batch of them: the frames this library writes end at 2 MiB a block chain, where that is a fraction of the parse.
+inline KSeekXxhArgs kx_frame_xxh_args(KBatchView const& v)
+{
+    KSeekXxhArgs x = { v.src, v.in_off, v.in_len, v.n, v.cks, nullptr, nullptr };
+    return x;
+}
+// its grid of four-wave workgroups: a wave takes 16 slices a trip (the shape the seekable container launches the body with)
+inline u32 kx_frame_xxh_blocks(u32 n) { u32 const b = (n + 63u) / 64u; return b < 1u ? 1u : b > 8192u ? 8192u : b; }
 
 // Entropy sweeps beside a one-block parse (zstd_compress_dfast): the parse leaves a completion record per slice and counts them
 // (KMatchArgs.done / done_count); a sweep is the entropy launch with KXE_SWEEP, which codes the slices that are done and not yet
@@ -169,6 +187,7 @@ inline KFrameArgs kx_frame_args(KBatchView const& v, KFrameState* fstate, u32* h
     e.stream = stream; e.strategy = b.strategy ? 1u : 0u; e.level2 = b.strategy == 2u ? 1u : 0u; e.cls = KXC_ALL;
     e.fast_step0 = b.strategy == 1u ? b.fast_step0 : 0u;
     e.tail_direct = stream == KXF_REFERENCE ? 0u : tail_or_chunk; e.out_chunk = stream == KXF_REFERENCE ? tail_or_chunk : 0u;
+    e.fflags = v.fflags; e.cks = v.cks;
     return e;
 }
 // Levels 5 .. 10 over frames of several blocks (zstd_lazy_big.h): the view's slices over table slots of slot_bytes each and their

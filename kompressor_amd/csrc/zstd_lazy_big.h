@@ -39,6 +39,16 @@ KX_DEV KLazyBigPar kx_lazy_big_params(u32 level, u32 n)
     p.rowLog = p.S < 4u ? 4u : p.S > 6u ? 6u : p.S;
     return p;
 }
+// ... and level 4's one "greedy" row above a block: ZSTD_getCParams(4, 128 KiB < n <= 256 KiB) = { 18, 16, 17, 3, 5, 2, greedy } (its other rows
+// above 16 KiB are double-fast: kx_params_l4).  n > 2^17, so neither clamp to the source applies.  One-shot frames only.
+KX_DEV KLazyBigPar kx_lazy_big_params_l4(u32 n)
+{
+    KLazyBigPar p; p.W = 0; p.H = 0; p.S = 0; p.mml = 0; p.strat = 0; p.rowLog = 0;
+    if (n > KX_BLOCK_MAX && n <= 262144u) { p.W = 18; p.H = 17; p.S = 3; p.mml = 5; p.strat = 3; p.rowLog = 4; }
+    return p;
+}
+// what the one-shot chain kernel runs a slice with at a.level
+KX_DEV KLazyBigPar kx_lazy_big_params_one_shot(u32 level, u32 n) { return level == 4u ? kx_lazy_big_params_l4(n) : kx_lazy_big_params(level, n); }
 // A stream (size unknown when the frame starts) gets the unknown-size row whatever its length turns out to be, 0 .. 2 MiB: the row above
 // 256 KiB without the clamps to the source size, minMatch 5 (tests/golden/zstd_lazy_stream_golden.json "params")
 KX_DEV KLazyBigPar kx_lazy_big_params_stream(u32 level, u32 n)
@@ -296,7 +306,7 @@ KX_DEV void zstd_lazy_big_body(const KLazyBigArgs& a)
         u32 const slice = kx_xcd_chunk(it, a.e.n_slices);
         if (a.e.fstate[slice].blockSize == 0) continue;                      // (uniform)
         u32 const n = a.e.in_len[slice];
-        KLazyBigPar const P = MODES ? kx_lazy_big_params_mode(a.level, n, a.e.stream) : kx_lazy_big_params(a.level, n);
+        KLazyBigPar const P = MODES ? kx_lazy_big_params_mode(a.level, n, a.e.stream) : kx_lazy_big_params_one_shot(a.level, n);
         if (P.strat == 0) continue;                                          // (cannot happen: the init kernel applies the same rule)
         const u8* const src = a.e.src + a.e.in_off[slice];
         u8* const slot = a.tables + (u64)slice * a.slot_bytes;
@@ -337,8 +347,8 @@ KX_DEV void zstd_lazy_big_init_slice(u32 len, KFrameState& s, KSeqPrev& pv, bool
     else if (streaming && !refused) s.blockSize = len;
 }
 // the empty stream at levels 5 .. 10: no content size, the level's window descriptor, an empty last block (9 bytes)
-KX_DEV u32 zstd_lazy_big_empty_stream(u8* d, u32 level)
+KX_DEV u32 zstd_lazy_big_empty_stream(u8* d, u32 level, u32 fflags = 0)
 {
-    kx_st32(d, 0xFD2FB528u); d[4] = 0; d[5] = (u8)((kx_lazy_big_params_stream(level, 0).W - 10u) << 3); d[6] = 1; d[7] = 0; d[8] = 0;
+    kx_st32(d, 0xFD2FB528u); d[4] = (u8)((fflags & KXH_CHECKSUM) ? 1u << 2 : 0u); d[5] = (u8)((kx_lazy_big_params_stream(level, 0).W - 10u) << 3); d[6] = 1; d[7] = 0; d[8] = 0;
     return 9u;
 }

@@ -12,6 +12,9 @@ from . import _lib
 from .slice_transform import ByteArraySlice, SliceTransform
 
 COMPRESSION_LEVEL = 100          # ZstdParameter.compressionLevel (ZstdParameter.kt:4)
+CONTENT_SIZE_FLAG = 200          # ZstdParameter.contentSizeFlag
+CHECKSUM_FLAG = 201              # ZstdParameter.checksumFlag
+DICT_ID_FLAG = 202               # ZstdParameter.dictIDFlag
 
 
 def _check_error_result(lib, result):
@@ -30,9 +33,11 @@ class ZstdCompressor(SliceTransform):
     """ZstdCompressor(compressionLevel, dictionary) of the reference: ZSTD_CCtx_setParameter + ZSTD_CCtx_loadDictionary, then frames through
     kmp_zstd_compress_stream.  With a dictionary (raw content or zstd's own format, 8 .. 130 560 bytes) levels 1, 2, 3 and the negative
     ones are served for what arrives in one closing call of at most 128 KiB; levels 4 .. 10, larger slices and input that arrived with
-    finish = false are refused with a dictionary ("Unsupported parameter") when the stream closes."""
+    finish = false are refused with a dictionary ("Unsupported parameter") when the stream closes.
+    checksum / content_size / dict_id: ZSTD_c_checksumFlag, ZSTD_c_contentSizeFlag and ZSTD_c_dictIDFlag, set through the cctx's parameters
+    when they differ from libzstd's defaults (no checksum; the content size and a formatted dictionary's ID in the header)."""
 
-    def __init__(self, compression_level=3, dictionary=None):
+    def __init__(self, compression_level=3, dictionary=None, checksum=False, content_size=True, dict_id=True):
         lib = self._lib = _lib.load()
         self._cctx = lib.kmp_zstd_create_cctx()
         if not self._cctx:
@@ -40,6 +45,9 @@ class ZstdCompressor(SliceTransform):
         # createCleaner(cctx, freeCompressor): freed by the GC, possibly on another thread
         self._cleaner = weakref.finalize(self, lib.kmp_zstd_free_cctx, self._cctx)
         _check_error_result(lib, lib.kmp_zstd_cctx_set_parameter(self._cctx, COMPRESSION_LEVEL, compression_level))
+        for param, value, default in ((CHECKSUM_FLAG, checksum, False), (CONTENT_SIZE_FLAG, content_size, True), (DICT_ID_FLAG, dict_id, True)):
+            if bool(value) != default:
+                _check_error_result(lib, lib.kmp_zstd_cctx_set_parameter(self._cctx, param, 1 if value else 0))
         if dictionary is not None:
             _check_error_result(lib, lib.kmp_zstd_cctx_load_dictionary(self._cctx, bytes(dictionary), len(dictionary)))
 
